@@ -19,6 +19,11 @@ launched under torch.distributed.run with one rank per GPU (TP=N over RCCL).
 W untimed warmup steps, then EXACTLY K timed steps bracketed by barrier +
 torch.cuda.synchronize on both sides; MAX over ranks; rank 0 prints ONE JSON
 line. TP splits one fixed model -> scaling is "strong".
+
+A plain run does only that. `--dump-outputs DIR` also writes the token ids
+the last timed step returned (prompts, weights and sampling are seeded, so
+two builds given the same arguments can be compared output for output).
+`--full` adds whatever is measured beyond the headline figure.
 """
 
 from __future__ import annotations
@@ -74,6 +79,20 @@ SYSTEM = (
 )
 
 
+def dump_outputs(out_dir: str, outputs: list) -> None:
+    """Write the token ids one timed step returned, one row per request."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    lens = np.array([len(o) for o in outputs], dtype=np.float32)
+    ids = np.full((len(outputs), int(lens.max()) if len(outputs) else 0), -1.0,
+                  dtype=np.float32)
+    for r, o in enumerate(outputs):
+        ids[r, : len(o)] = o
+    np.save(os.path.join(out_dir, "output_ids.npy"), ids)
+    np.save(os.path.join(out_dir, "output_lens.npy"), lens)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -95,6 +114,16 @@ def main() -> None:
                     help="'auto' = assets/tokenizer-32k.json when present "
                          "(trained BPE, scripts/train_tokenizer.py), "
                          "'byte' = byte-level, or a tokenizer.json path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed "
+                         "step returned to its caller as DIR/<name>.npy "
+                         "(float32): output_ids [requests, max_len] padded "
+                         "with -1, output_lens [requests]")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure; a plain run "
+                         "only sets up, warms up, times the steps and prints "
+                         "the result line. Today the one extra is the stage "
+                         "perf table (--breakdown)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -167,6 +196,7 @@ def main() -> None:
 
     valid = 0
     total_prefill_tokens = 0
+    last_outputs: list = []  # token-id lists the last timed step returned
 
     if world > 1 and rank != 0:
         # Followers never see the request stream: rank 0
@@ -209,6 +239,7 @@ def main() -> None:
                     torch.cuda.synchronize()
                 times.append((time.perf_counter() - ts) * 1000.0)
                 check_valid(out)
+                last_outputs[:] = [out]
                 total_prefill_tokens += args.prompt_tokens
             return times
 
@@ -249,6 +280,7 @@ def main() -> None:
                     torch.cuda.synchronize()
                 times.append((time.perf_counter() - ts) * 1000.0)
                 check_valid(out)
+                last_outputs[:] = [out]
             return times
 
     else:  # concurrent
@@ -278,6 +310,7 @@ def main() -> None:
                 times.extend([dt] * n)  # per-turn latency of the wave
                 for out, _ in results:
                     check_valid(out)
+                last_outputs[:] = [out for out, _ in results]
                 total_prefill_tokens += n * args.prompt_tokens
                 done += n
             return times
@@ -339,8 +372,10 @@ def main() -> None:
         }
         if args.moe_dtype:
             result["config"]["moe_dtype"] = args.moe_dtype
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_outputs)
         print(json.dumps(result))
-        if args.breakdown:
+        if args.breakdown or args.full:
             from opsagent_amd.utils.perf import get_perf_stats
 
             print(get_perf_stats().format_table(), file=sys.stderr)
