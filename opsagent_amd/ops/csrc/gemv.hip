@@ -11,10 +11,20 @@
 // x is tiny (8-56 KB) and L1-resident after the first pass — each lane
 // re-reads only its own 16-B slices, so no LDS staging is needed.
 //
-// Requires K % 512 == 0 (64 lanes x 8 bf16); callers fall back to hipBLASLt
-// otherwise (and for M > 8, where the MFMA path wins).
+// K pipeline: one 16-B load per lane and trip keeps RW KiB per wave in
+// flight, and a row then costs K/512 serial HBM round trips. The K loop
+// instead walks pieces of KU * 64 16-B units (gemv_tile.h): a wave issues the
+// piece's x (and norm-weight) loads and its KU W loads per row back to back,
+// then consumes the slots in order — KU * RW KiB in flight per wave, K/(512
+// KU) round trips per row. Each (row, m) keeps ONE accumulator fed in
+// ascending K, low half before high half, so every depth is bit-identical to
+// depth 1.
+//
+// Requires K % 8 == 0 (16-B units); callers fall back to hipBLASLt otherwise
+// (and for M > 8, where the MFMA path wins).
 
 #include "common.h"
+#include "gemv_tile.h"
 #include <cstdlib>
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
@@ -41,11 +51,186 @@ __device__ __forceinline__ float row_rstd(const uint32_t* xrow, int k2, int lane
     return rsqrtf(ss / (float)(k2 * 2) + eps);
 }
 
+// ---- K pipeline (piece geometry: gemv_tile.h) -------------------------------
+// A row is walked in pieces of D unit-rows (D * 64 16-B units): KU deep while
+// that many whole unit-rows are left, then 4, 2, 1 as they fit, so every such piece is
+// free of per-load predicates and its slots sit at immediate offsets from one
+// address. Only the partial unit-row of a K % 512 != 0 shape is predicated
+// (depth 1): a dead lane loads nothing and feeds zeros — fmaf(0, 0, acc)
+// leaves acc untouched. All arrays are indexed by unrolled constants only, so
+// they live in VGPRs.
+
+// Keeps the scheduler from hoisting every slot's bf16 unpacking above the
+// first FMA: unfenced, the consume of a deep piece holds all its unpacked
+// floats at once and the VGPR count (hence resident waves) suffers.
+#define GEMV_SLOT_FENCE() __builtin_amdgcn_sched_barrier(0)
+
+__device__ __forceinline__ u32x4 ld4(const uint32_t* p) {
+    return *reinterpret_cast<const u32x4*>(p);
+}
+
+// one rstd piece: D x loads in flight, then the single ss chain in K order
+template <int D, bool PARTIAL>
+__device__ __forceinline__ float rstd_piece(const uint32_t* xrow, int k2, int r,
+                                            int lane, float ss) {
+    const uint32_t* p = xrow + gemv_slot_word(r, 0, lane);  // slot s: + s * 256
+    u32x4 xv[D];
+#pragma unroll
+    for (int s = 0; s < D; ++s) {
+        if (PARTIAL) xv[s] = u32x4{0u, 0u, 0u, 0u};
+        if (!PARTIAL || gemv_partial_live(k2, lane)) xv[s] = ld4(p + s * 256);
+    }
+#pragma unroll
+    for (int s = 0; s < D; ++s) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float lo = bf16_lo(xv[s][j]), hi = bf16_hi(xv[s][j]);
+            ss = fmaf(lo, lo, ss);
+            ss = fmaf(hi, hi, ss);
+        }
+        GEMV_SLOT_FENCE();
+    }
+    return ss;
+}
+
+// row_rstd for the fused-norm VALU GEMVs: the same single `ss` chain in
+// ascending K, but XD 16-B x loads are in flight before the first is consumed
+// (K = 4096 is ONE trip at XD = 8) instead of one L2 round trip per load.
+template <int XD>
+__device__ __forceinline__ float row_rstd_pipe(const uint32_t* xrow, int k2,
+                                               int lane, float eps) {
+    float ss = 0.0f;
+    int r = 0;
+    for (int d; (d = gemv_piece_depth(k2, XD, r)) > 0; r += d) {
+        if (d == XD) ss = rstd_piece<XD, false>(xrow, k2, r, lane, ss);
+        else if (XD > 4 && d == 4) ss = rstd_piece<4, false>(xrow, k2, r, lane, ss);
+        else if (XD > 2 && d == 2) ss = rstd_piece<2, false>(xrow, k2, r, lane, ss);
+        else ss = rstd_piece<1, false>(xrow, k2, r, lane, ss);
+    }
+    if (gemv_slot_word(r, 0, 0) < k2) ss = rstd_piece<1, true>(xrow, k2, r, lane, ss);
+    ss = wave_reduce_sum(ss);
+    return rsqrtf(ss / (float)(k2 * 2) + eps);
+}
+
+// One piece of one row group: issue D W loads per row and the matching x
+// (and norm-weight) loads back to back, then consume the slots in order —
+// one accumulator per (row, m), ascending K, low half before high half, i.e.
+// the order of the one-load-per-trip loop.
+//
+// NORM: W does not depend on rstd, so on a wave's first piece the W loads go
+// out FIRST and the whole rstd prologue (x loads, ss chain, wave reduction)
+// runs under their HBM latency; `need_rstd` is wave-uniform.
+//
+// M > 2 (depth 1, not on the hot path) reads x inside the consume loop as the
+// original kernel did, to keep its register footprint.
+template <int M, bool NORM, int RW, int D, int XD, bool PARTIAL>
+__device__ __forceinline__ void gemv_piece_step(
+    float (&acc)[RW][M], float (&rstd)[M], bool& need_rstd,
+    const uint32_t* (&wr)[RW], const uint32_t* x, const uint32_t* wn, int k2,
+    int r, int lane, float eps) {
+    constexpr bool XPRE = M == 1;
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+    const bool on = !PARTIAL || gemv_partial_live(k2, lane);
+    const int i0 = gemv_slot_word(r, 0, lane);  // slot s: + s * 256 words
+
+    u32x4 wv[D][RW], xv[D][M], nv[D];
+    if (XPRE && !NORM) {
+#pragma unroll
+        for (int s = 0; s < D; ++s)
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                if (PARTIAL) xv[s][m] = zero;
+                if (on) xv[s][m] = ld4(x + (size_t)m * k2 + i0 + s * 256);
+            }
+    }
+    // stream W non-temporally: each byte is read exactly once per step; keep
+    // L2 for the KV cache and activations
+#pragma unroll
+    for (int s = 0; s < D; ++s)
+#pragma unroll
+        for (int rr_ = 0; rr_ < RW; ++rr_) {
+            if (PARTIAL) wv[s][rr_] = zero;
+            if (on) wv[s][rr_] = nt_load4(wr[rr_] + i0 + s * 256);
+        }
+    if (NORM) {
+        if (need_rstd) {
+#pragma unroll
+            for (int m = 0; m < M; ++m)
+                rstd[m] = row_rstd_pipe<XD>(x + (size_t)m * k2, k2, lane, eps);
+            need_rstd = false;
+        }
+        if (XPRE) {
+#pragma unroll
+            for (int s = 0; s < D; ++s) {
+#pragma unroll
+                for (int m = 0; m < M; ++m) {
+                    if (PARTIAL) xv[s][m] = zero;
+                    if (on) xv[s][m] = ld4(x + (size_t)m * k2 + i0 + s * 256);
+                }
+                if (PARTIAL) nv[s] = zero;
+                if (on) nv[s] = ld4(wn + i0 + s * 256);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int s = 0; s < D; ++s) {
+        u32x4 nq = zero;
+        if (NORM) {
+            if (XPRE) nq = nv[s];
+            else if (on) nq = ld4(wn + i0 + s * 256);
+        }
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            u32x4 xq = zero;
+            if (XPRE) xq = xv[s][m];
+            else if (on) xq = ld4(x + (size_t)m * k2 + i0 + s * 256);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float xl = bf16_lo(xq[j]), xh = bf16_hi(xq[j]);
+                if (NORM) {
+                    const uint32_t wnw = nq[j];
+                    xl *= rstd[m] * bf16_lo(wnw);
+                    xh *= rstd[m] * bf16_hi(wnw);
+                }
+#pragma unroll
+                for (int rr_ = 0; rr_ < RW; ++rr_) {
+                    acc[rr_][m] = fmaf(xl, bf16_lo(wv[s][rr_][j]), acc[rr_][m]);
+                    acc[rr_][m] = fmaf(xh, bf16_hi(wv[s][rr_][j]), acc[rr_][m]);
+                }
+            }
+        }
+        GEMV_SLOT_FENCE();
+    }
+}
+
+// all pieces of one row group: KU deep, then the 4/2/1-deep tail, then the
+// partial unit-row if K % 512 != 0
+template <int M, bool NORM, int RW, int KU, int XD>
+__device__ __forceinline__ void gemv_row_pieces(
+    float (&acc)[RW][M], float (&rstd)[M], bool& need_rstd,
+    const uint32_t* (&wr)[RW], const uint32_t* x, const uint32_t* wn, int k2,
+    int lane, float eps) {
+#define GEMV_STEP(DV, PV)                                                      \
+    gemv_piece_step<M, NORM, RW, DV, XD, PV>(acc, rstd, need_rstd, wr, x, wn,  \
+                                             k2, r, lane, eps)
+    int r = 0;
+    for (int d; (d = gemv_piece_depth(k2, KU, r)) > 0; r += d) {
+        if (d == KU) GEMV_STEP(KU, false);
+        else if (KU > 4 && d == 4) GEMV_STEP(4, false);
+        else if (KU > 2 && d == 2) GEMV_STEP(2, false);
+        else GEMV_STEP(1, false);
+    }
+    if (gemv_slot_word(r, 0, 0) < k2) GEMV_STEP(1, true);
+#undef GEMV_STEP
+}
+
 // NORM: x is normalized on the fly (rstd prologue + norm-weight multiply) —
 // the separate rmsnorm kernel and its output round-trip disappear.
 // ADDRES: the epilogue adds a residual row — out = x @ W^T + residual, i.e.
 // the new residual stream is produced directly by the projection.
-template <int M, bool NORM, bool ADDRES, int RW = 2>
+// KU: 16-B W loads per row in flight per K tile (1 = one load per trip).
+template <int M, bool NORM, bool ADDRES, int RW = 2, int KU = 1>
 __global__ __launch_bounds__(256) void gemv_kernel(
     const uint32_t* __restrict__ x,  // [M, K/2]
     const uint32_t* __restrict__ w,  // [N, K/2]
@@ -53,13 +238,19 @@ __global__ __launch_bounds__(256) void gemv_kernel(
     const uint32_t* __restrict__ wn, // [K/2] rmsnorm weight (NORM only)
     const uint32_t* __restrict__ res,// [M, N] residual (ADDRES only)
     int N, int k2 /* K/2 */, float eps) {
+    // rstd prologue depth: K = 4096 in one trip where the registers allow
+    constexpr int XD = (RW == 1 && KU <= 4 && M == 1) ? 8 : 4;
     const int lane = threadIdx.x & (WAVE - 1);
     const int wid = threadIdx.x / WAVE;
 
     float rstd[M];
-    if (NORM) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) rstd[m] = 1.0f;
+    bool need_rstd = NORM;
+    if (NORM && M > 2) {  // depth-1 forms: the plain prologue, up front
 #pragma unroll
         for (int m = 0; m < M; ++m) rstd[m] = row_rstd(x + (size_t)m * k2, k2, lane, eps);
+        need_rstd = false;
     }
 
     // RW adjacent W rows per wave: multiplies the outstanding 16-B streams
@@ -78,31 +269,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(
         for (int rr_ = 0; rr_ < RW; ++rr_)
 #pragma unroll
             for (int m = 0; m < M; ++m) acc[rr_][m] = 0.0f;
-        for (int i = lane * 4; i < k2; i += WAVE * 4) {
-            // stream W non-temporally: each byte is read exactly once per
-            // step; keep L2 for the KV cache and activations
-            u32x4 wv[RW];
-#pragma unroll
-            for (int rr_ = 0; rr_ < RW; ++rr_) wv[rr_] = nt_load4(wr[rr_] + i);
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                uint4 xv = *reinterpret_cast<const uint4*>(x + (size_t)m * k2 + i);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float xl = bf16_lo((&xv.x)[j]), xh = bf16_hi((&xv.x)[j]);
-                    if (NORM) {
-                        const uint32_t wnw = wn[i + j];
-                        xl *= rstd[m] * bf16_lo(wnw);
-                        xh *= rstd[m] * bf16_hi(wnw);
-                    }
-#pragma unroll
-                    for (int rr_ = 0; rr_ < RW; ++rr_) {
-                        acc[rr_][m] = fmaf(xl, bf16_lo(wv[rr_][j]), acc[rr_][m]);
-                        acc[rr_][m] = fmaf(xh, bf16_hi(wv[rr_][j]), acc[rr_][m]);
-                    }
-                }
-            }
-        }
+        gemv_row_pieces<M, NORM, RW, KU, XD>(acc, rstd, need_rstd, wr, x, wn, k2,
+                                            lane, eps);
 #pragma unroll
         for (int m = 0; m < M; ++m) {
 #pragma unroll
@@ -124,54 +292,46 @@ __global__ __launch_bounds__(256) void gemv_kernel(
 // Fused gate-up + SiLU GEMV for the MLP up-projection: the fused weight
 // holds gate rows [0, I) and up rows [I, 2I); each wave computes BOTH rows
 // r and I + r and writes act[m][r] = silu(gate) * up directly — the separate
-// [1, 2I] intermediate and the silu_mul pass never materialize.
-template <int M, bool NORM>
-__global__ __launch_bounds__(256) void gemv_gateup_kernel(
+// [1, 2I] intermediate and the silu_mul pass never materialize. The K
+// pipeline is the two-row one above with (gate, up) as the row pair.
+// (the M = 2 fused-norm form is held to the 6 waves per SIMD of its M = 2
+// siblings; left alone the compiler spends 88 VGPRs on it)
+template <int M, bool NORM, int KU = 1>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(M == 2 && NORM && KU == 1 ? 6 : 1)))
+void gemv_gateup_kernel(
     const uint32_t* __restrict__ x,  // [M, K/2]
     const uint32_t* __restrict__ w,  // [2I, K/2] (gate; up)
     uint32_t* __restrict__ out,      // [M, I] bf16
     const uint32_t* __restrict__ wn, // [K/2] rmsnorm weight (NORM only)
     int I, int k2, float eps) {
+    constexpr int XD = M == 1 ? 4 : 2;
     const int lane = threadIdx.x & (WAVE - 1);
     const int wid = threadIdx.x / WAVE;
 
     float rstd[M];
-    if (NORM) {
+#pragma unroll
+    for (int m = 0; m < M; ++m) rstd[m] = 1.0f;
+    bool need_rstd = NORM;
+    if (NORM && M > 2) {  // depth-1 forms: the plain prologue, up front
 #pragma unroll
         for (int m = 0; m < M; ++m) rstd[m] = row_rstd(x + (size_t)m * k2, k2, lane, eps);
+        need_rstd = false;
     }
 
     for (int row = blockIdx.x * 4 + wid; row < I; row += gridDim.x * 4) {
-        const uint32_t* grow = w + (size_t)row * k2;
-        const uint32_t* urow = w + (size_t)(I + row) * k2;
-        float accg[M], accu[M];
+        const uint32_t* wr[2];
+        wr[0] = w + (size_t)row * k2;
+        wr[1] = w + (size_t)(I + row) * k2;
+        float acc[2][M];  // [0] gate, [1] up
 #pragma unroll
-        for (int m = 0; m < M; ++m) accg[m] = accu[m] = 0.0f;
-        for (int i = lane * 4; i < k2; i += WAVE * 4) {
-            u32x4 gv = nt_load4(grow + i);
-            u32x4 uv = nt_load4(urow + i);
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                uint4 xv = *reinterpret_cast<const uint4*>(x + (size_t)m * k2 + i);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float xl = bf16_lo((&xv.x)[j]), xh = bf16_hi((&xv.x)[j]);
-                    if (NORM) {
-                        const uint32_t wnw = wn[i + j];
-                        xl *= rstd[m] * bf16_lo(wnw);
-                        xh *= rstd[m] * bf16_hi(wnw);
-                    }
-                    accg[m] = fmaf(xl, bf16_lo(gv[j]), accg[m]);
-                    accg[m] = fmaf(xh, bf16_hi(gv[j]), accg[m]);
-                    accu[m] = fmaf(xl, bf16_lo(uv[j]), accu[m]);
-                    accu[m] = fmaf(xh, bf16_hi(uv[j]), accu[m]);
-                }
-            }
-        }
+        for (int m = 0; m < M; ++m) acc[0][m] = acc[1][m] = 0.0f;
+        gemv_row_pieces<M, NORM, 2, KU, XD>(acc, rstd, need_rstd, wr, x, wn, k2,
+                                           lane, eps);
 #pragma unroll
         for (int m = 0; m < M; ++m) {
-            const float g = wave_reduce_sum(accg[m]);
-            const float u = wave_reduce_sum(accu[m]);
+            const float g = wave_reduce_sum(acc[0][m]);
+            const float u = wave_reduce_sum(acc[1][m]);
             if (lane == 0) {
                 const float act = g / (1.0f + __expf(-g)) * u;
                 reinterpret_cast<uint16_t*>(out)[(size_t)m * I + row] = f32_to_bf16(act);
@@ -186,6 +346,119 @@ extern "C" int oa_gemv_bf16_mfma(void* stream, const void* x, const void* w,
                                  int M, int N, int K, float eps, int mode,
                                  int gateup);
 
+// ---- K-depth dispatch (M <= 2, the decode hot path) -------------------------
+// Depth per dispatch class and M, chosen by measurement at M = 1
+// (scripts/gemv_depth_ab.py, then the in-model A/B; profiles/README.md
+// "K-depth pipeline") under the register budget tests/test_gemv_resources.py
+// gates: a depth must leave as many waves resident as the class's grid
+// supplies. M = 2 takes the deepest form that fits the same budget. The
+// M = 3..16 instantiations stay at depth 1: they exist for tests, not for the
+// hot path. OPSAGENT_GEMV_KU_<CLASS> overrides a class for both M.
+#define GEMV_KU_RW1_M1 8       // one row per wave, small N: o_proj, down
+#define GEMV_KU_RW1_M2 8
+#define GEMV_KU_RW1_NORM_M1 2  // the same with the fused norm: qkv
+#define GEMV_KU_RW1_NORM_M2 2
+#define GEMV_KU_RW2_M1 1       // two rows per wave: lm_head, 70B shapes
+#define GEMV_KU_RW2_M2 1
+#define GEMV_KU_RW2_NORM_M1 1
+#define GEMV_KU_RW2_NORM_M2 1
+#define GEMV_KU_GATEUP_M1 1    // (gate, up) row pair per wave
+#define GEMV_KU_GATEUP_M2 1
+
+// env override of a class's depth, 0 when unset or not one of 1/2/4/8
+static int gemv_env_ku(const char* name) {
+    const char* e = getenv(name);
+    if (!e) return 0;
+    const int v = atoi(e);
+    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0;
+}
+
+struct GemvArgs {
+    hipStream_t stream;
+    const uint32_t *x, *w;
+    uint32_t* out;
+    const uint32_t *wn, *res;
+    int N, k2;  // gate-up: N holds I
+    float eps;
+    int grid;
+};
+
+template <int M, int RW, int KU>
+static int gemv_launch_mode(const GemvArgs& a, int mode) {
+#define LAUNCH_KU(NORMV, RESV)                                                 \
+    hipLaunchKernelGGL((gemv_kernel<M, NORMV, RESV, RW, KU>), dim3(a.grid),    \
+                       dim3(256), 0, a.stream, a.x, a.w, a.out, a.wn, a.res,   \
+                       a.N, a.k2, a.eps)
+    switch (mode) {
+        case 0: LAUNCH_KU(false, false); break;
+        case 1: LAUNCH_KU(true, false); break;
+        case 2: LAUNCH_KU(false, true); break;
+        case 3: LAUNCH_KU(true, true); break;
+        default: return -102;
+    }
+#undef LAUNCH_KU
+    return 0;
+}
+
+template <int M, int RW>
+static int gemv_launch_ku(const GemvArgs& a, int mode, int ku) {
+    switch (ku) {
+        case 1: return gemv_launch_mode<M, RW, 1>(a, mode);
+        case 2: return gemv_launch_mode<M, RW, 2>(a, mode);
+        case 4: return gemv_launch_mode<M, RW, 4>(a, mode);
+        case 8: return gemv_launch_mode<M, RW, 8>(a, mode);
+        default: return -103;
+    }
+}
+
+// M in {1, 2}, rw in {1, 2}, ku in {1, 2, 4, 8}
+static int gemv_launch_m12(const GemvArgs& a, int M, int mode, int rw, int ku) {
+    if (M == 1) return rw == 1 ? gemv_launch_ku<1, 1>(a, mode, ku)
+                               : gemv_launch_ku<1, 2>(a, mode, ku);
+    return rw == 1 ? gemv_launch_ku<2, 1>(a, mode, ku)
+                   : gemv_launch_ku<2, 2>(a, mode, ku);
+}
+
+template <int M, int KU>
+static void gemv_gateup_launch(const GemvArgs& a, int norm) {
+    if (norm)
+        hipLaunchKernelGGL((gemv_gateup_kernel<M, true, KU>), dim3(a.grid),
+                           dim3(256), 0, a.stream, a.x, a.w, a.out, a.wn, a.N,
+                           a.k2, a.eps);
+    else
+        hipLaunchKernelGGL((gemv_gateup_kernel<M, false, KU>), dim3(a.grid),
+                           dim3(256), 0, a.stream, a.x, a.w, a.out, a.wn, a.N,
+                           a.k2, a.eps);
+}
+
+template <int M>
+static int gemv_gateup_launch_ku(const GemvArgs& a, int norm, int ku) {
+    switch (ku) {
+        case 1: gemv_gateup_launch<M, 1>(a, norm); break;
+        case 2: gemv_gateup_launch<M, 2>(a, norm); break;
+        case 4: gemv_gateup_launch<M, 4>(a, norm); break;
+        case 8: gemv_gateup_launch<M, 8>(a, norm); break;
+        default: return -103;
+    }
+    return 0;
+}
+
+// probe/test entry: gate-up at an explicit K depth (M <= 2, VALU kernel only)
+extern "C" int oa_gemv_gateup_ku(void* stream, const void* x, const void* w,
+                                 void* out, const void* wn, int M, int I, int K,
+                                 float eps, int norm, int ku) {
+    if (K % 8 != 0 || K < 8) return -100;
+    if (M < 1 || M > 2 || I < 1) return -101;
+    const GemvArgs a = {(hipStream_t)stream, (const uint32_t*)x, (const uint32_t*)w,
+                        (uint32_t*)out, (const uint32_t*)wn, nullptr, I, K / 2, eps,
+                        min(2048, CEIL_DIV(I, 4))};
+    const int rc = M == 1 ? gemv_gateup_launch_ku<1>(a, norm, ku)
+                          : gemv_gateup_launch_ku<2>(a, norm, ku);
+    if (rc != 0) return rc;
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int oa_gemv_gateup_ex(void* stream, const void* x, const void* w,
                                  void* out, const void* wn, int M, int I, int K,
                                  float eps, int norm) {
@@ -193,6 +466,12 @@ extern "C" int oa_gemv_gateup_ex(void* stream, const void* x, const void* w,
     if (gemv_bf16_use_mfma(M, K, 1))
         return oa_gemv_bf16_mfma(stream, x, w, out, wn, nullptr, M, 2 * I, K,
                                  eps, norm ? 1 : 0, 1);
+    if (M <= 2) {
+        static const int env_ku = gemv_env_ku("OPSAGENT_GEMV_KU_GATEUP");
+        const int ku = env_ku ? env_ku
+                              : (M == 1 ? GEMV_KU_GATEUP_M1 : GEMV_KU_GATEUP_M2);
+        return oa_gemv_gateup_ku(stream, x, w, out, wn, M, I, K, eps, norm, ku);
+    }
     const int k2 = K / 2;
     const int grid = min(2048, CEIL_DIV(I, 4));
 #define LAUNCH_GU(MV)                                                          \
@@ -209,8 +488,6 @@ extern "C" int oa_gemv_gateup_ex(void* stream, const void* x, const void* w,
                                (uint32_t*)out, (const uint32_t*)wn, I, k2, eps);\
     } while (0)
     switch (M) {
-        case 1: LAUNCH_GU(1); break;
-        case 2: LAUNCH_GU(2); break;
         case 3: LAUNCH_GU(3); break;
         case 4: LAUNCH_GU(4); break;
         case 5: LAUNCH_GU(5); break;
@@ -231,6 +508,23 @@ extern "C" int oa_gemv_gateup(void* stream, const void* x, const void* w,
     return oa_gemv_gateup_ex(stream, x, w, out, nullptr, M, I, K, 0.0f, 0);
 }
 
+// probe/test entry: plain/norm/residual GEMV at an explicit rows-per-wave and
+// K depth (M <= 2, VALU kernel only; same grids as the dispatcher)
+extern "C" int oa_gemv_ku(void* stream, const void* x, const void* w, void* out,
+                          const void* wn, const void* res, int M, int N, int K,
+                          float eps, int mode, int rw, int ku) {
+    if (K % 8 != 0 || K < 8) return -100;
+    if (M < 1 || M > 2 || N < 1) return -101;
+    if (rw != 1 && rw != 2) return -104;
+    const GemvArgs a = {(hipStream_t)stream, (const uint32_t*)x, (const uint32_t*)w,
+                        (uint32_t*)out, (const uint32_t*)wn, (const uint32_t*)res,
+                        N, K / 2, eps, min(2048, CEIL_DIV(N, 4 * rw))};
+    const int rc = gemv_launch_m12(a, M, mode, rw, ku);
+    if (rc != 0) return rc;
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
 // mode: 0 plain, 1 norm-prologue, 2 residual-add epilogue, 3 both
 extern "C" int oa_gemv_ex(void* stream, const void* x, const void* w, void* out,
                           const void* wn, const void* res, int M, int N, int K,
@@ -247,9 +541,13 @@ extern "C" int oa_gemv_ex(void* stream, const void* x, const void* w, void* out,
     // re-enables for experiments.
     static int rw4_min_n = -1;
     static int rw1_max_n = -1;
+    static int env_rw1 = 0, env_rw1n = 0, env_rw2 = 0, env_rw2n = 0;
     if (rw4_min_n < 0) {
-        const char* e = getenv("OPSAGENT_GEMV_RW4_MIN_N");
-        rw4_min_n = e ? atoi(e) : (1 << 30);
+        // K depth per class (see GEMV_KU_*); env overrides for experiments
+        env_rw1 = gemv_env_ku("OPSAGENT_GEMV_KU_RW1");
+        env_rw1n = gemv_env_ku("OPSAGENT_GEMV_KU_RW1_NORM");
+        env_rw2 = gemv_env_ku("OPSAGENT_GEMV_KU_RW2");
+        env_rw2n = gemv_env_ku("OPSAGENT_GEMV_KU_RW2_NORM");
         // RW=1 for small-N outputs: at N=4096 the RW=2 grid is only 512
         // workgroups (2 per CU — half the SIMD slots idle); one row per wave
         // doubles the wave count and the streams in flight. In-model A/B
@@ -257,9 +555,21 @@ extern "C" int oa_gemv_ex(void* stream, const void* x, const void* w, void* out,
         // 431.9 ms — default N<=6144 (covers o_proj and the fused-norm qkv).
         const char* e1 = getenv("OPSAGENT_GEMV_RW1_MAX_N");
         rw1_max_n = e1 ? atoi(e1) : 6144;
+        const char* e = getenv("OPSAGENT_GEMV_RW4_MIN_N");
+        rw4_min_n = e ? atoi(e) : (1 << 30);
     }
     const bool rw4 = N >= rw4_min_n;
     const bool rw1 = !rw4 && N <= rw1_max_n;
+    if (M <= 2 && !rw4) {
+        const bool norm = mode & 1, m1 = M == 1;
+        int ku;
+        if (rw1 && !norm) ku = env_rw1 ? env_rw1 : (m1 ? GEMV_KU_RW1_M1 : GEMV_KU_RW1_M2);
+        else if (rw1) ku = env_rw1n ? env_rw1n : (m1 ? GEMV_KU_RW1_NORM_M1 : GEMV_KU_RW1_NORM_M2);
+        else if (!norm) ku = env_rw2 ? env_rw2 : (m1 ? GEMV_KU_RW2_M1 : GEMV_KU_RW2_M2);
+        else ku = env_rw2n ? env_rw2n : (m1 ? GEMV_KU_RW2_NORM_M1 : GEMV_KU_RW2_NORM_M2);
+        return oa_gemv_ku(stream, x, w, out, wn, res, M, N, K, eps, mode,
+                          rw1 ? 1 : 2, ku);
+    }
     const int grid = min(2048, CEIL_DIV(N, rw4 ? 16 : (rw1 ? 4 : 8)));
 #define LAUNCH_NM(MV, NORMV, RESV)                                            \
     do {                                                                       \

@@ -51,6 +51,11 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.oa_gemv_ex.restype = i
     lib.oa_gemv_gateup_ex.argtypes = [p, p, p, p, p, i, i, i, f, i]
     lib.oa_gemv_gateup_ex.restype = i
+    # probe/test entries: explicit rows-per-wave and K depth (M <= 2)
+    lib.oa_gemv_ku.argtypes = [p, p, p, p, p, p, i, i, i, f, i, i, i]
+    lib.oa_gemv_ku.restype = i
+    lib.oa_gemv_gateup_ku.argtypes = [p, p, p, p, p, i, i, i, f, i, i]
+    lib.oa_gemv_gateup_ku.restype = i
     lib.oa_masked_argmax.argtypes = [p, p, p, p, p, i, i]
     lib.oa_masked_argmax.restype = i
     lib.oa_attention_prefill.argtypes = [p, p, p, p, p, i, i, i, i, i, i, f, i, i, i]
