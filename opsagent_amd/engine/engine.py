@@ -23,6 +23,7 @@ Architecture:
 from __future__ import annotations
 
 import dataclasses
+import os
 import time
 from typing import Dict, List, Optional, Tuple
 
@@ -240,6 +241,25 @@ class LLMEngine:
             # the cache
             self.model.quantize_fp8_()
 
+        # KV cache element type: "bf16" (default) or "fp8" (OCP e4m3 codes +
+        # one f32 scale per (slot, kv-head) row — 132 B against 256 B, so a
+        # KV budget holds 1.94x the tokens and batched decode attention
+        # reads half the bytes). The environment variable applies only when
+        # the config key is absent.
+        kvd = cfg.get("kv_cache_dtype")
+        if kvd is None:
+            kvd = os.environ.get("OPSAGENT_KV_CACHE_DTYPE") or "bf16"
+        self.kv_cache_dtype = str(kvd).lower()
+        if self.kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError(
+                f"kv_cache_dtype must be 'bf16' or 'fp8', got {kvd!r}"
+            )
+        if self.kv_cache_dtype == "fp8" and self.spec.head_dim != 128:
+            raise ValueError("kv_cache_dtype fp8 needs head_dim 128")
+        if self.kv_cache_dtype == "fp8" and self.block_size < 4:
+            # the fp8 decode kernel reads two block-table entries per key quad
+            raise ValueError("kv_cache_dtype fp8 needs kv_block_size >= 4")
+
         num_blocks = self._pick_num_blocks(cfg)
         if self.tp > 1:
             # ranks must agree on cache geometry (free-VRAM probes can differ
@@ -255,7 +275,8 @@ class LLMEngine:
         self.kv = PagedKVCache(
             self.spec.num_layers, hk_local, self.spec.head_dim,
             self.block_size, num_blocks, self.device,
-            torch.bfloat16 if self.device == "cuda" else self.dtype,
+            "fp8" if self.kv_cache_dtype == "fp8"
+            else (torch.bfloat16 if self.device == "cuda" else self.dtype),
         )
         self.max_blocks_per_seq = (self.max_seq_len + self.block_size - 1) // self.block_size
 
@@ -314,8 +335,9 @@ class LLMEngine:
             return int(cfg["kv_num_blocks"])
         kv_gb = float(cfg.get("kv_cache_gb", 0) or 0)
         hk_local = self.spec.num_kv_heads // self.tp
-        block_bytes = (
-            2 * self.spec.num_layers * self.block_size * hk_local * self.spec.head_dim * 2
+        block_bytes = PagedKVCache.block_bytes(
+            self.spec.num_layers, hk_local, self.spec.head_dim, self.block_size,
+            self.kv_cache_dtype == "fp8",
         )
         if self.device == "cpu":
             blocks_needed = self.max_batch * (
@@ -591,7 +613,7 @@ class LLMEngine:
                 seq.all_slots(start + count).to(dev, dtype=torch.int64) if start > 0 else None
             ),
         )
-        hidden = self.model(fb, self.kv.layers)
+        hidden = self.model(fb, self.kv.layers, self.kv.scales)
         seq.num_cached = start + count
         seq.publish_full_blocks()
         req.prefill_done = start + count
@@ -628,7 +650,7 @@ class LLMEngine:
             prefill_past_len=start,
             prefill_slot_gather=seq.all_slots(total).to(dev, dtype=torch.int64),
         )
-        hidden = self.model(fb, self.kv.layers)
+        hidden = self.model(fb, self.kv.layers, self.kv.scales)
         seq.num_cached = total
         seq.publish_full_blocks()
         logits = self.model.compute_logits(hidden[-1:])
@@ -712,7 +734,7 @@ class LLMEngine:
             prefill_past_len=start,
             prefill_slot_gather=seq.all_slots(total).to(dev, dtype=torch.int64),
         )
-        hidden = self.model(fb, self.kv.layers)
+        hidden = self.model(fb, self.kv.layers, self.kv.scales)
         logits = self.model.compute_logits(hidden)
         gs = req.grammar_state
         if gs is None:
@@ -967,7 +989,7 @@ class LLMEngine:
     def _decode_eager(self, B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu):
         self._fill_static(B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu, B)
         fb = self._make_decode_fb(B)
-        hidden = self.model(fb, self.kv.layers)
+        hidden = self.model(fb, self.kv.layers, self.kv.scales)
         return self.model.compute_logits(hidden)
 
     def _decode_graphed(self, B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu):
@@ -982,13 +1004,13 @@ class LLMEngine:
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
                     for _ in range(2):
-                        hidden = self.model(fb, self.kv.layers)
+                        hidden = self.model(fb, self.kv.layers, self.kv.scales)
                         logits = self.model.compute_logits(hidden)
                 torch.cuda.current_stream().wait_stream(s)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    hidden = self.model(fb, self.kv.layers)
+                    hidden = self.model(fb, self.kv.layers, self.kv.scales)
                     logits = self.model.compute_logits(hidden)
                 self._graphs[bucket] = (g, logits)
                 log.info("captured decode hipGraph for batch bucket %d", bucket)
@@ -1282,4 +1304,7 @@ class LLMEngine:
 
     # -- info -------------------------------------------------------------
     def cache_stats(self) -> dict:
-        return dict(self.kv.stats, free_blocks=self.kv.num_free())
+        return dict(
+            self.kv.stats, free_blocks=self.kv.num_free(),
+            kv_cache_dtype=self.kv_cache_dtype,
+        )

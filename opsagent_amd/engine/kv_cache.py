@@ -17,7 +17,7 @@ cached (refcount 0) in LRU order and are evicted on allocation pressure.
 from __future__ import annotations
 
 import collections
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -35,19 +35,38 @@ class PagedKVCache:
         block_size: int,
         num_blocks: int,
         device: str,
-        dtype: torch.dtype = torch.bfloat16,
+        dtype: Union[torch.dtype, str] = torch.bfloat16,
     ):
+        """dtype "fp8": `layers` holds uint8 OCP e4m3 codes and `scales` the
+        parallel per-layer (k_scale, v_scale) float32 [num_blocks, block_size,
+        Hk] tensors, one scale per (slot, kv-head) row. Scales are indexed by
+        the same block ids as the codes, so the allocator and the prefix
+        cache carry them along untouched. For any torch dtype `scales` is
+        None."""
         assert block_size & (block_size - 1) == 0, "block_size must be a power of 2"
         self.block_size = block_size
         self.num_blocks = num_blocks
         self.device = device
+        self.fp8 = dtype == "fp8"
+        self.dtype_name = "fp8" if self.fp8 else str(dtype).replace("torch.", "")
+        if self.fp8:
+            dtype = torch.uint8
         self.layers: List[Tuple[torch.Tensor, torch.Tensor]] = []
+        self.scales: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = (
+            [] if self.fp8 else None
+        )
         for _ in range(num_layers):
             k = torch.zeros(
                 num_blocks, block_size, num_kv_heads_local, head_dim, dtype=dtype, device=device
             )
             v = torch.zeros_like(k)
             self.layers.append((k, v))
+            if self.fp8:
+                ks = torch.zeros(
+                    num_blocks, block_size, num_kv_heads_local,
+                    dtype=torch.float32, device=device,
+                )
+                self.scales.append((ks, torch.zeros_like(ks)))
         # allocator state
         self._free: collections.deque[int] = collections.deque(range(num_blocks))
         self._ref: List[int] = [0] * num_blocks
@@ -62,6 +81,17 @@ class PagedKVCache:
         # LRU of refcount-0 cached blocks (evictable)
         self._evictable: "collections.OrderedDict[int, None]" = collections.OrderedDict()
         self.stats = {"reused_blocks": 0, "allocated_blocks": 0, "evictions": 0}
+
+    @staticmethod
+    def block_bytes(
+        num_layers: int, num_kv_heads_local: int, head_dim: int,
+        block_size: int, fp8: bool,
+    ) -> int:
+        """Bytes one block occupies across all layers, K and V: 2 B per
+        element for bf16; 1 B per element plus a 4-B scale per (slot, head)
+        row for fp8 (132 B against 256 B per row at head_dim 128)."""
+        row = head_dim + 4 if fp8 else head_dim * 2
+        return 2 * num_layers * block_size * num_kv_heads_local * row
 
     # -- low-level allocator ----------------------------------------------
     def num_free(self) -> int:

@@ -68,6 +68,17 @@ class ForwardBatch:
     seq_lens: Optional[torch.Tensor] = None     # [B] int32
     decode_workspace: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
     nsplit: Optional[int] = None
+    # fp8 KV prefill: int32 slots of every key (past + new), made once per
+    # step by gather_slots() and shared by all layers
+    gather_slots_i32: Optional[torch.Tensor] = None
+
+    def gather_slots(self) -> torch.Tensor:
+        if self.gather_slots_i32 is None:
+            self.gather_slots_i32 = (
+                self.prefill_slot_gather.to(torch.int32)
+                if self.prefill_past_len > 0 else self.slot_mapping
+            )
+        return self.gather_slots_i32
 
 
 def _shard(t: torch.Tensor, dim: int, rank: int, size: int) -> torch.Tensor:
@@ -134,6 +145,7 @@ class Attention(nn.Module):
         k_cache: torch.Tensor,
         v_cache: torch.Tensor,
         fb: ForwardBatch,
+        kv_scale: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
     ) -> torch.Tensor:
         T = x.shape[0]
         qkv = self._qkv(x)  # hipBLASLt / HIP gemv / fp8 at decode
@@ -147,6 +159,9 @@ class Attention(nn.Module):
         v = v.view(T, self.hk, self.hd)
         if not x.is_cuda:
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if kv_scale is not None:
+            out = self._attend_fp8(q, k, v, cos, sin, k_cache, v_cache, kv_scale, fb)
+            return tp_all_reduce(self._o(out.view(T, self.hq * self.hd)))
         if fb.kind == "decode" and x.is_cuda and _rope_attn_fused():
             # fully-fused decode attention (RoPE + KV scatter in-kernel)
             out = ops.attention_decode_rope(
@@ -189,6 +204,31 @@ class Attention(nn.Module):
             out = out.view(T, self.hq * self.hd)
         out = self._o(out)
         return tp_all_reduce(out)
+
+
+    def _attend_fp8(self, q, k, v, cos, sin, k_codes, v_codes, kv_scale, fb):
+        """fp8 KV cache: quantising write, then attention over the cache's
+        OWN (dequantised) values. Prefill gathers every key — the new ones
+        included, also at past_len == 0 — so a prefix-cache hit and a cold
+        prefill attend over the same K and V. Decode is the unfused
+        write-then-attend form (the rope-fused decode is bf16 only)."""
+        k_scale, v_scale = kv_scale
+        q, k, v = ops.rope_kv_fused_fp8(
+            q, k, v, k_codes, v_codes, k_scale, v_scale, cos, sin,
+            fb.positions, fb.slot_mapping,
+        )
+        if fb.kind == "prefill":
+            k_full, v_full = ops.kv_gather_fp8(
+                k_codes, v_codes, k_scale, v_scale, fb.gather_slots(), dtype=q.dtype
+            )
+            return ops.attention_prefill(
+                q.unsqueeze(0), k_full.unsqueeze(0), v_full.unsqueeze(0),
+                scale=self.scale,
+            )
+        return ops.attention_decode_paged_fp8(
+            q, k_codes, v_codes, k_scale, v_scale, fb.block_table, fb.seq_lens,
+            scale=self.scale, workspace=fb.decode_workspace, nsplit=fb.nsplit,
+        )
 
 
 class DenseMLP(nn.Module):
@@ -237,13 +277,13 @@ class DecoderLayer(nn.Module):
         else:
             self.mlp = DenseMLP(spec, dtype, gen)
 
-    def forward(self, x, residual, cos, sin, k_cache, v_cache, fb):
+    def forward(self, x, residual, cos, sin, k_cache, v_cache, fb, kv_scale=None):
         if residual is None:
             residual = x
             h = ops.rms_norm(x, self.input_norm_w, self.eps)
         else:
             h, residual = ops.fused_add_rms_norm(x, residual, self.input_norm_w, self.eps)
-        a = self.attn(h, cos, sin, k_cache, v_cache, fb)
+        a = self.attn(h, cos, sin, k_cache, v_cache, fb, kv_scale)
         h, residual = ops.fused_add_rms_norm(a, residual, self.post_norm_w, self.eps)
         if self.is_moe_layer:
             m = self.mlp(h, decode=fb.kind == "decode")
@@ -251,7 +291,7 @@ class DecoderLayer(nn.Module):
             m = self.mlp(h)
         return m, residual
 
-    def fused_decode(self, residual, cos, sin, k_cache, v_cache, fb):
+    def fused_decode(self, residual, cos, sin, k_cache, v_cache, fb, kv_scale=None):
         """Decode with norms fused into GEMV prologues and residual adds into
         GEMV epilogues (see LlamaForCausalLM._use_fused_decode). Takes and
         returns the residual stream."""
@@ -267,7 +307,11 @@ class DecoderLayer(nn.Module):
         q = q.view(T, at.hq, at.hd)
         k = k.view(T, at.hk, at.hd)
         v = v.view(T, at.hk, at.hd)
-        if _rope_attn_fused():
+        if kv_scale is not None:
+            ctx = at._attend_fp8(
+                q, k, v, cos, sin, k_cache, v_cache, kv_scale, fb
+            ).view(T, at.hq * at.hd)
+        elif _rope_attn_fused():
             ctx = ops.attention_decode_rope(
                 q, k, v, k_cache, v_cache, fb.block_table, fb.seq_lens,
                 cos, sin, fb.slot_mapping, scale=at.scale,
@@ -406,7 +450,14 @@ class LlamaForCausalLM(nn.Module):
         if self.embed.is_cuda:
             torch.cuda.empty_cache()
 
-    def forward(self, fb: ForwardBatch, kv_caches: List[Tuple[torch.Tensor, torch.Tensor]]):
+    def forward(
+        self,
+        fb: ForwardBatch,
+        kv_caches: List[Tuple[torch.Tensor, torch.Tensor]],
+        kv_scales: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None,
+    ):
+        """kv_scales: per-layer (k_scale, v_scale) of an fp8 paged cache
+        (PagedKVCache.scales); None for a bf16 cache."""
         x = F.embedding(fb.input_ids, self.embed)
         if self._use_fused_decode(fb, x):
             residual = x.contiguous()
@@ -414,6 +465,7 @@ class LlamaForCausalLM(nn.Module):
                 residual = layer.fused_decode(
                     residual, self.rope_cos, self.rope_sin,
                     kv_caches[i][0], kv_caches[i][1], fb,
+                    kv_scales[i] if kv_scales is not None else None,
                 )
             return ops.rms_norm(residual, self.final_norm_w, self.spec.rms_eps)
         residual = None
@@ -421,6 +473,7 @@ class LlamaForCausalLM(nn.Module):
             x, residual = layer(
                 x, residual, self.rope_cos, self.rope_sin,
                 kv_caches[i][0], kv_caches[i][1], fb,
+                kv_scales[i] if kv_scales is not None else None,
             )
         x, _ = ops.fused_add_rms_norm(x, residual, self.final_norm_w, self.spec.rms_eps)
         return x  # [T, hidden]

@@ -28,6 +28,9 @@ __all__ = [
     "kv_cache_write",
     "attention_prefill",
     "attention_decode_paged",
+    "rope_kv_fused_fp8",
+    "kv_gather_fp8",
+    "attention_decode_paged_fp8",
     "greedy_sample_masked",
     "rope_cos_sin",
 ]
@@ -440,6 +443,137 @@ def rope_kv_fused(
     )
     hip.check(rc, "oa_rope_kv")
     return q, k, v
+
+
+def rope_kv_fused_fp8(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    k_codes: torch.Tensor,
+    v_codes: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    positions: torch.Tensor,
+    slot_mapping: torch.Tensor,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """rope_kv_fused for the fp8 paged cache: RoPE(q, k in place), then the
+    roped k (as rounded to bf16) and v are quantised per (token, head) row to
+    OCP e4m3 and scattered with their scales. codes uint8 [num_blocks,
+    block_size, Hk, 128], scales f32 [num_blocks, block_size, Hk]. q/k/v may
+    be head-slices of the fused qkv buffer. Returns (q, k, v)."""
+    if not _is_gpu(q):
+        return torch_ref.rope_kv_fp8(
+            q, k, v, k_codes, v_codes, k_scale, v_scale, cos, sin, positions,
+            slot_mapping,
+        )
+    T, Hq, D = q.shape
+    Hk = k.shape[1]
+    assert q.dtype == torch.bfloat16
+    assert q.stride(2) == 1 and q.stride(1) == D, "q heads must be inner-contiguous"
+    assert k.stride(2) == 1 and k.stride(1) == D and v.stride(2) == 1 and v.stride(1) == D
+    assert k_codes.dtype == torch.uint8 and v_codes.dtype == torch.uint8
+    assert k_codes.is_contiguous() and v_codes.is_contiguous()
+    assert k_scale.dtype == torch.float32 and v_scale.dtype == torch.float32
+    assert k_scale.is_contiguous() and v_scale.is_contiguous()
+    assert k_codes.shape[2] == Hk and k_scale.shape == k_codes.shape[:3]
+    assert cos.dtype == torch.float32
+    assert positions.dtype == torch.int32 and slot_mapping.dtype == torch.int32
+    lib, hip = _lib()
+    rc = lib.oa_rope_kv_fp8(
+        hip.current_stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        k_codes.data_ptr(), v_codes.data_ptr(), k_scale.data_ptr(),
+        v_scale.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+        positions.data_ptr(), slot_mapping.data_ptr(), T, Hq, Hk, D,
+        q.stride(0), k.stride(0), v.stride(0),
+    )
+    hip.check(rc, "oa_rope_kv_fp8")
+    return q, k, v
+
+
+def kv_gather_fp8(
+    k_codes: torch.Tensor,
+    v_codes: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    slots: torch.Tensor,
+    dtype: torch.dtype = torch.bfloat16,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Gather the given flat slots from the fp8 paged cache and dequantise:
+    contiguous [Skv, Hk, 128] K and V, value = bf16(float(code) * scale), in
+    one launch. `dtype` applies to the CPU reference only (GPU is bf16)."""
+    if not _is_gpu(k_codes):
+        return torch_ref.kv_gather_fp8(k_codes, v_codes, k_scale, v_scale, slots, dtype)
+    nb, bs, Hk, D = k_codes.shape
+    assert k_codes.dtype == torch.uint8 and k_codes.is_contiguous()
+    assert v_codes.dtype == torch.uint8 and v_codes.is_contiguous()
+    assert k_scale.dtype == torch.float32 and k_scale.is_contiguous()
+    assert v_scale.dtype == torch.float32 and v_scale.is_contiguous()
+    slots = slots.to(torch.int32).contiguous()
+    Skv = slots.shape[0]
+    lib, hip = _lib()
+    k_out = torch.empty(Skv, Hk, D, dtype=torch.bfloat16, device=k_codes.device)
+    v_out = torch.empty_like(k_out)
+    rc = lib.oa_kv_gather_fp8(
+        hip.current_stream_ptr(), k_codes.data_ptr(), v_codes.data_ptr(),
+        k_scale.data_ptr(), v_scale.data_ptr(), slots.data_ptr(),
+        k_out.data_ptr(), v_out.data_ptr(), Skv, Hk, D,
+    )
+    hip.check(rc, "oa_kv_gather_fp8")
+    return k_out, v_out
+
+
+def attention_decode_paged_fp8(
+    q: torch.Tensor,
+    k_codes: torch.Tensor,
+    v_codes: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    block_table: torch.Tensor,
+    seq_lens: torch.Tensor,
+    scale: Optional[float] = None,
+    workspace: Optional[Tuple[torch.Tensor, ...]] = None,
+    nsplit: Optional[int] = None,
+) -> torch.Tensor:
+    """attention_decode_paged over the fp8 paged cache (two-kernel form:
+    split-K attention with in-register dequant, then the shared combine).
+    q [B, Hq, 128] bf16; codes uint8 [num_blocks, block_size, Hk, 128];
+    scales f32 [num_blocks, block_size, Hk]; out [B, Hq, 128] bf16."""
+    if not _is_gpu(q):
+        return torch_ref.attention_decode_paged_fp8(
+            q, k_codes, v_codes, k_scale, v_scale, block_table, seq_lens, scale
+        )
+    assert q.dtype == torch.bfloat16
+    assert q.stride(2) == 1 and q.stride(1) == q.shape[2], "q heads must be inner-contiguous"
+    assert block_table.dtype == torch.int32 and seq_lens.dtype == torch.int32
+    assert k_codes.dtype == torch.uint8 and k_codes.is_contiguous()
+    assert v_codes.dtype == torch.uint8 and v_codes.is_contiguous()
+    assert k_scale.dtype == torch.float32 and k_scale.is_contiguous()
+    assert v_scale.dtype == torch.float32 and v_scale.is_contiguous()
+    B, Hq, D = q.shape
+    nb, block_size, Hk, _ = k_codes.shape
+    assert block_size >= 4, "the fp8 decode kernel needs block_size >= 4"
+    G = Hq // Hk
+    scale = scale if scale is not None else D ** -0.5
+    if nsplit is None:
+        nsplit = decode_nsplit(B, Hk, int(block_table.shape[1] * block_size))
+    if workspace is None:
+        o_part = torch.empty(B * Hk * nsplit, G, D, dtype=torch.float32, device=q.device)
+        ml_part = torch.empty(B * Hk * nsplit, G, 2, dtype=torch.float32, device=q.device)
+    else:
+        o_part, ml_part = workspace[0], workspace[1]
+    lib, hip = _lib()
+    out = torch.empty(B, Hq, D, dtype=q.dtype, device=q.device)
+    rc = lib.oa_attention_decode_fp8(
+        hip.current_stream_ptr(), q.data_ptr(), k_codes.data_ptr(),
+        v_codes.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+        block_table.data_ptr(), seq_lens.data_ptr(), o_part.data_ptr(),
+        ml_part.data_ptr(), out.data_ptr(), B, Hq, Hk, D,
+        block_table.shape[1], block_size, nsplit, scale, q.stride(0),
+    )
+    hip.check(rc, "oa_attention_decode_fp8")
+    return out
 
 
 def gateup_silu(x: torch.Tensor, gate_up_w: torch.Tensor, i_local: int) -> torch.Tensor:

@@ -25,6 +25,7 @@ SOURCES = [
     "attention_prefill.hip",
     "fp8_moe.hip",
     "moe_gemv.hip",
+    "kv_fp8.hip",
 ]
 
 HIPCC = os.environ.get("HIPCC", "hipcc")
@@ -47,7 +48,9 @@ def needs_rebuild() -> bool:
     out_t = _mtime(OUT)
     if out_t == 0.0:
         return True
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "common.h")]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + [
+        os.path.join(CSRC, h) for h in ("common.h", "decode_combine.h")
+    ]
     return any(_mtime(d) > out_t for d in deps)
 
 

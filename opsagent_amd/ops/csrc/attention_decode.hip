@@ -531,6 +531,29 @@ extern "C" int oa_attention_decode(void* stream, const void* q, const void* kc,
     return 0;
 }
 
+// The combine alone, for kernels in other files that publish partials in the
+// same (o_part, ml_part) layout — see decode_combine.h.
+extern "C" int oa_decode_combine(void* stream, const void* o_part,
+                                 const void* ml_part, void* out, int B, int Hq,
+                                 int Hk, int nsplit) {
+    dim3 cgrid(B * Hq), cblock(512);
+    const int clds = nsplit * 2 * (int)sizeof(float);
+#define LAUNCH_C(GV)                                                            \
+    hipLaunchKernelGGL((decode_combine_kernel<GV>), cgrid, cblock, clds,        \
+                       (hipStream_t)stream, (const float*)o_part,               \
+                       (const float*)ml_part, (uint32_t*)out, B, Hk, nsplit)
+    switch (Hq / Hk) {
+        case 1: LAUNCH_C(1); break;
+        case 2: LAUNCH_C(2); break;
+        case 4: LAUNCH_C(4); break;
+        case 8: LAUNCH_C(8); break;
+        default: return -102;
+    }
+#undef LAUNCH_C
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
 // Fully-fused decode attention: RoPE(q, k) + paged-KV scatter of (k, v) +
 // split-K attention in ONE launch (+ the combine kernel) — replaces the
 // separate rope_kv launch per layer. q/kin/vin are the RAW (un-roped) GEMV

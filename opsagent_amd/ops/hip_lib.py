@@ -67,6 +67,15 @@ def _declare(lib: ctypes.CDLL) -> None:
         i, i, i, i, i, i, i, f, i, i, i,
     ]
     lib.oa_attention_decode_rope.restype = i
+    # fp8 paged KV cache (kv_fp8.hip)
+    lib.oa_rope_kv_fp8.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i]
+    lib.oa_rope_kv_fp8.restype = i
+    lib.oa_kv_gather_fp8.argtypes = [p, p, p, p, p, p, p, p, i, i, i]
+    lib.oa_kv_gather_fp8.restype = i
+    lib.oa_attention_decode_fp8.argtypes = [
+        p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, f, i,
+    ]
+    lib.oa_attention_decode_fp8.restype = i
     lib.oa_quant_fp8.argtypes = [p, p, p, p, i, i]
     lib.oa_quant_fp8.restype = i
     lib.oa_gemv_fp8.argtypes = [p, p, p, p, p, i, i, i]

@@ -166,6 +166,71 @@ def dequant_fp8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return f * scale.unsqueeze(-1)
 
 
+def rope_kv_fp8(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    k_codes: torch.Tensor,
+    v_codes: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    positions: torch.Tensor,
+    slot_mapping: torch.Tensor,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """RoPE(q, k), then quantise roped k and v per (token, head) row and
+    scatter codes + scales into the fp8 paged cache.
+
+    codes: uint8 [num_blocks, block_size, Hk, D]; scales: f32 [num_blocks,
+    block_size, Hk]. Returns (roped q, roped k, v)."""
+    q2, k2 = rope_apply(q, k, cos, sin, positions)
+    nb, bs, hk, d = k_codes.shape
+    slots = slot_mapping.long()
+    for x, codes, scales in ((k2, k_codes, k_scale), (v, v_codes, v_scale)):
+        c, s = quant_fp8(x)                       # [T, Hk, D], [T*Hk]
+        codes.view(nb * bs, hk, d)[slots] = c
+        scales.view(nb * bs, hk)[slots] = s.view(-1, hk)
+    return q2, k2, v
+
+
+def kv_gather_fp8(
+    k_codes: torch.Tensor,
+    v_codes: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    slots: torch.Tensor,
+    dtype: torch.dtype = torch.bfloat16,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Gather + dequantise: [Skv, Hk, D] K and V with value
+    dtype(float(code) * scale) for the given flat slots."""
+    nb, bs, hk, d = k_codes.shape
+    idx = slots.long()
+    outs = []
+    for codes, scales in ((k_codes, k_scale), (v_codes, v_scale)):
+        c = codes.view(nb * bs, hk, d)[idx]
+        s = scales.view(nb * bs, hk)[idx]
+        outs.append(dequant_fp8(c, s).to(dtype))
+    return outs[0], outs[1]
+
+
+def attention_decode_paged_fp8(
+    q: torch.Tensor,
+    k_codes: torch.Tensor,
+    v_codes: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    block_table: torch.Tensor,
+    seq_lens: torch.Tensor,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """Decode attention over the fp8 paged cache: dequantise, then the
+    reference paged attention."""
+    kc = dequant_fp8(k_codes, k_scale)
+    vc = dequant_fp8(v_codes, v_scale)
+    return attention_decode_paged(q, kc, vc, block_table, seq_lens, scale)
+
+
 def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor) -> torch.Tensor:
     w = dequant_fp8(w8, w_scale)
     return torch.nn.functional.linear(x.float(), w).to(x.dtype)
