@@ -155,7 +155,12 @@ class LLMEngine:
         # jump-ahead applies only in the low-concurrency latency regime.
         self.grammar_fastforward = bool(cfg.get("grammar_fastforward", True))
         self.grammar_ff_min_run = int(cfg.get("grammar_ff_min_run", 3))
-        self.grammar_ff_max_batch = int(cfg.get("grammar_ff_max_batch", 4))
+        # the environment variable applies only when the config key is absent
+        # (measurement through an unmodified benchmark)
+        ffmb = cfg.get("grammar_ff_max_batch")
+        if ffmb is None:
+            ffmb = os.environ.get("OPSAGENT_GRAMMAR_FF_MAX_BATCH") or 4
+        self.grammar_ff_max_batch = int(ffmb)
         # speculative n-gram (prompt-lookup) decoding: propose the tokens
         # that followed the most recent occurrence of the trailing n-gram,
         # verify all of them in ONE multi-token forward, commit the accepted
@@ -320,6 +325,31 @@ class LLMEngine:
             )
         else:
             self._dec_ws = None
+
+        # append attention: catch-up and verify passes (a few new tokens of
+        # a sequence against its cached past) read the paged cache in place
+        # through ops.attention_append_paged instead of gathering the whole
+        # past for the prefill kernel, and a catch-up shares its step with
+        # the ordinary decode rows. Off by default; the environment variable
+        # applies only when the config key is absent.
+        aa = cfg.get("append_attention")
+        if aa is None:
+            aa = os.environ.get("OPSAGENT_APPEND_ATTN", "") == "1"
+        self.append_attention = bool(aa)
+        self._append_cap = ops.append_max_q(G)
+        if self.append_attention and self.kv_cache_dtype == "fp8":
+            log.warning("append_attention is ignored with kv_cache_dtype fp8")
+            self.append_attention = False
+        if self.append_attention and (
+            self._append_cap < 1
+            or (self.device == "cuda" and self.spec.head_dim != 128)
+        ):
+            log.warning(
+                "append_attention needs head_dim 128 and a GQA group of "
+                "1, 2, 4 or 8 — ignored"
+            )
+            self.append_attention = False
+        self._append_ws: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         self._graphs: Dict[int, Tuple[torch.cuda.CUDAGraph, torch.Tensor]] = {}
 
         self.requests: Dict[int, Request] = {}
@@ -537,6 +567,8 @@ class LLMEngine:
             None,
         )
         if catchup is not None:
+            if self.append_attention and self._append_step():
+                return
             self._catchup_forward(catchup)
             return
 
@@ -660,6 +692,110 @@ class LLMEngine:
         )
         self._sample_and_append([req], logits)
 
+    # -- append attention ---------------------------------------------------
+    def _append_fb(self, rows: List[Tuple[SequenceState, int, List[int]]]) -> ForwardBatch:
+        """ForwardBatch of kind "append": row (seq, start, ids) pushes
+        len(ids) <= append cap tokens at positions start.. against seq's
+        cached past. Capacity for start + len(ids) must already be ensured."""
+        dev = self.device
+        ids_all: List[int] = []
+        pos_all: List[int] = []
+        slots = []
+        cu = [0]
+        lens = []
+        for seq, start, ids in rows:
+            ids_all.extend(ids)
+            pos_all.extend(range(start, start + len(ids)))
+            slots.append(seq.slots_for(start, len(ids)))
+            cu.append(cu[-1] + len(ids))
+            lens.append(start + len(ids))
+        B = len(rows)
+        bs = self.kv.block_size
+        width = max((n + bs - 1) // bs for n in lens)
+        bt_cpu = torch.zeros(B, width, dtype=torch.int32)
+        for i, (seq, _, _) in enumerate(rows):
+            nb = min(len(seq.blocks), width)
+            bt_cpu[i, :nb] = torch.tensor(seq.blocks[:nb], dtype=torch.int32)
+        max_q = max(len(ids) for _, _, ids in rows)
+        hk_local = self.spec.num_kv_heads // self.tp
+        nsplit = ops.decode_nsplit(B, max(hk_local, 1), max(lens))
+        ws = None
+        if dev == "cuda":
+            G = (self.spec.num_heads // self.tp) // hk_local
+            need = B * hk_local * nsplit * max_q * G
+            if self._append_ws is None or self._append_ws[1].shape[0] < need:
+                self._append_ws = ops.append_workspace(
+                    B, cu[-1], hk_local, G, nsplit, device=dev, max_q=max_q
+                )
+            ws = self._append_ws
+        return ForwardBatch(
+            kind="append",
+            input_ids=torch.tensor(ids_all, dtype=torch.int64, device=dev),
+            positions=torch.tensor(pos_all, dtype=torch.int32, device=dev),
+            slot_mapping=torch.cat(slots).to(dev),
+            block_table=bt_cpu.to(dev),
+            seq_lens=torch.tensor(lens, dtype=torch.int32, device=dev),
+            decode_workspace=ws,
+            nsplit=nsplit,
+            cu_q=torch.tensor(cu, dtype=torch.int32, device=dev),
+            max_q=max_q,
+        )
+
+    @torch.inference_mode()
+    def _append_step(self) -> bool:
+        """Mixed step: every request owing a catch-up of at most the append
+        cap (L = tokens owed) and every decode-ready request (L = 1) share
+        ONE forward through the append attention kernel; each row samples
+        from its last token. Returns False — nothing done — when no catch-up
+        fits the cap (the caller then takes the prefill-style catch-up)."""
+        t0 = time.perf_counter()
+        cap = self._append_cap
+        cand = []
+        for r in self.running:
+            if r.finished or r.prefill_done < len(r.prompt_ids) or r.spec_tokens:
+                continue
+            owed = len(r.seq.token_ids) - r.seq.num_cached
+            if 1 <= owed <= cap:
+                cand.append(r)
+        if not any(len(r.seq.token_ids) - r.seq.num_cached > 1 for r in cand):
+            return False
+        batch: List[Request] = []
+        for r in cand:
+            try:
+                r.seq.ensure_capacity(len(r.seq.token_ids))
+            except BlockAllocatorError:
+                self._preempt(r)
+                continue
+            batch.append(r)
+        if not batch:
+            self._reap()
+            return True
+        rows = []
+        caught = 0
+        for r in batch:
+            seq = r.seq
+            start, total = seq.num_cached, len(seq.token_ids)
+            rows.append((seq, start, seq.token_ids[start:total]))
+            if total - start > 1:
+                caught += total - start
+        fb = self._append_fb(rows)
+        hidden = self.model(fb, self.kv.layers, self.kv.scales)
+        last = (fb.cu_q[1:] - 1).long()
+        logits = self.model.compute_logits(hidden[last])
+        for r in batch:
+            r.seq.num_cached = len(r.seq.token_ids)
+            r.seq.publish_full_blocks()
+        self.perf.record_metric("engine_append_steps", 1.0)
+        self.perf.record_metric("engine_append_rows", float(len(batch)))
+        if caught:
+            self.perf.record_metric("engine_ff_catchup_tokens", float(caught))
+            self.perf.record_metric(
+                "engine_ff_catchup_ms", (time.perf_counter() - t0) * 1000.0
+            )
+        self._sample_and_append(batch, logits)
+        self._reap()
+        return True
+
     # -- speculative n-gram decoding --------------------------------------
     def _spec_eligible(self, req: Request) -> bool:
         return (
@@ -726,14 +862,20 @@ class LLMEngine:
             self._preempt(req)
             return
         dev = self.device
-        fb = ForwardBatch(
-            kind="prefill",
-            input_ids=torch.tensor(ids, dtype=torch.int64, device=dev),
-            positions=torch.arange(start, total, dtype=torch.int32, device=dev),
-            slot_mapping=seq.slots_for(start, len(ids)).to(dev),
-            prefill_past_len=start,
-            prefill_slot_gather=seq.all_slots(total).to(dev, dtype=torch.int64),
-        )
+        if self.append_attention and len(ids) <= self._append_cap:
+            # one append row: the past is read from the paged cache in place
+            fb = self._append_fb([(seq, start, ids)])
+            self.perf.record_metric("engine_append_steps", 1.0)
+            self.perf.record_metric("engine_append_rows", 1.0)
+        else:
+            fb = ForwardBatch(
+                kind="prefill",
+                input_ids=torch.tensor(ids, dtype=torch.int64, device=dev),
+                positions=torch.arange(start, total, dtype=torch.int32, device=dev),
+                slot_mapping=seq.slots_for(start, len(ids)).to(dev),
+                prefill_past_len=start,
+                prefill_slot_gather=seq.all_slots(total).to(dev, dtype=torch.int64),
+            )
         hidden = self.model(fb, self.kv.layers, self.kv.scales)
         logits = self.model.compute_logits(hidden)
         gs = req.grammar_state
@@ -1307,4 +1449,5 @@ class LLMEngine:
         return dict(
             self.kv.stats, free_blocks=self.kv.num_free(),
             kv_cache_dtype=self.kv_cache_dtype,
+            append_attention=self.append_attention,
         )

@@ -53,10 +53,13 @@ class ForwardBatch:
     """Metadata for one engine step.
 
     prefill: one sequence of T new tokens (with optional cached past);
-    decode: B sequences, one new token each.
+    decode: B sequences, one new token each;
+    append: B sequences, sequence b with cu_q[b+1]-cu_q[b] <= max_q new
+    tokens attending the paged cache in place (block_table, seq_lens and
+    nsplit as for decode; decode_workspace holds the append workspace).
     """
 
-    kind: str  # "prefill" | "decode"
+    kind: str  # "prefill" | "decode" | "append"
     input_ids: torch.Tensor      # [T] int64
     positions: torch.Tensor      # [T] int32
     slot_mapping: torch.Tensor   # [T] int32 — flat cache slots for new KV
@@ -71,6 +74,9 @@ class ForwardBatch:
     # fp8 KV prefill: int32 slots of every key (past + new), made once per
     # step by gather_slots() and shared by all layers
     gather_slots_i32: Optional[torch.Tensor] = None
+    # append only:
+    cu_q: Optional[torch.Tensor] = None         # [B+1] int32
+    max_q: int = 0
 
     def gather_slots(self) -> torch.Tensor:
         if self.gather_slots_i32 is None:
@@ -190,6 +196,12 @@ class Attention(nn.Module):
                 q.unsqueeze(0), k_full, v_full, scale=self.scale
             )
             out = out.view(T, self.hq * self.hd)
+        elif fb.kind == "append":
+            out = ops.attention_append_paged(
+                q, k_cache, v_cache, fb.block_table, fb.seq_lens, fb.cu_q,
+                fb.max_q, scale=self.scale, workspace=fb.decode_workspace,
+                nsplit=fb.nsplit,
+            ).view(T, self.hq * self.hd)
         else:
             out = ops.attention_decode_paged(
                 q,

@@ -720,6 +720,115 @@ def attention_decode_paged(
     return out
 
 
+_APPEND_MAX_Q = 16
+
+
+def append_max_q(group: int) -> int:
+    """Largest number of new query tokens per sequence the append kernel
+    serves at GQA group size `group` (0: the group size is unsupported)."""
+    return _APPEND_MAX_Q if group in (1, 2, 4, 8) else 0
+
+
+def append_partition(
+    n: int, q_len: int, group: int, nsplit: int, max_q: Optional[int] = None
+) -> list:
+    """The append kernel's own key partition for one sequence: a list, one
+    entry per split, of the (start, end) key sub-ranges its waves walk.
+    Rows R = q_len*group; with R <= 16*NRT (NRT = 1 when max_q*group <= 16,
+    else 2) the four waves split the split's keys in 32-key-aligned quarters,
+    otherwise they split row tiles and each walks the whole split."""
+    max_q = q_len if max_q is None else max_q
+    nrt = 1 if max_q * group <= 16 else 2
+    ntile = (min(q_len * group, max_q * group) + 15) // 16
+    chunk = (max(n, 0) + nsplit - 1) // nsplit
+    parts = []
+    for s in range(nsplit):
+        ks, ke = s * chunk, min(n, s * chunk + chunk)
+        if ntile <= nrt:
+            span = max(ke - ks, 0)
+            wchunk = (((span + 3) // 4) + 31) // 32 * 32
+            subs = []
+            for w in range(4):
+                ws = ks + w * wchunk
+                we = min(ke, ws + wchunk)
+                if we > ws:
+                    subs.append((ws, we))
+            parts.append(subs)
+        else:
+            parts.append([(ks, ke)] if ke > ks else [])
+    return parts
+
+
+def append_workspace(
+    b_max: int, t_max: int, n_kv_heads: int, group: int, nsplit: int,
+    device=None, max_q: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(o_part, ml_part) f32 workspaces for attention_append_paged: one slab
+    of max_q*group rows per (sequence, kv head, split). t_max is accepted for
+    symmetry with the engine's sizing; the slabs do not depend on it."""
+    del t_max
+    max_q = append_max_q(group) if max_q is None else max_q
+    rows = b_max * n_kv_heads * nsplit * max_q * group
+    o_part = torch.empty(rows, 128, dtype=torch.float32, device=device)
+    ml_part = torch.empty(rows, 2, dtype=torch.float32, device=device)
+    return o_part, ml_part
+
+
+def attention_append_paged(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    block_table: torch.Tensor,
+    seq_lens: torch.Tensor,
+    cu_q: torch.Tensor,
+    max_q: int,
+    scale: Optional[float] = None,
+    workspace: Optional[Tuple[torch.Tensor, ...]] = None,
+    nsplit: Optional[int] = None,
+) -> torch.Tensor:
+    """Append attention: B sequences, sequence b with L_b = cu_q[b+1]-cu_q[b]
+    new query tokens (1 <= L_b <= max_q <= append_max_q(G)) whose K/V are
+    already in the paged cache. q [T, Hq, 128] (heads inner-contiguous, any
+    token stride); seq_lens[b] counts all keys including the new ones; query
+    token j of b attends keys [0, seq_lens[b]-L_b+j]. Reads the cache in
+    place, split over keys like attention_decode_paged. out [T, Hq, 128]."""
+    if not _is_gpu(q):
+        return torch_ref.attention_append_paged(
+            q, k_cache, v_cache, block_table, seq_lens, cu_q, scale
+        )
+    assert q.dtype == torch.bfloat16
+    assert q.stride(2) == 1 and q.stride(1) == q.shape[2], "q heads must be inner-contiguous"
+    assert block_table.dtype == torch.int32 and seq_lens.dtype == torch.int32
+    assert cu_q.dtype == torch.int32 and cu_q.is_contiguous()
+    assert block_table.is_contiguous()
+    T, Hq, D = q.shape
+    B = seq_lens.shape[0]
+    assert cu_q.shape[0] == B + 1
+    nb, block_size, Hk, _ = k_cache.shape
+    G = Hq // Hk
+    scale = scale if scale is not None else D ** -0.5
+    if nsplit is None:
+        nsplit = decode_nsplit(B, Hk, int(block_table.shape[1] * block_size))
+    rows = B * Hk * nsplit * max_q * G
+    if workspace is None:
+        o_part = torch.empty(rows, D, dtype=torch.float32, device=q.device)
+        ml_part = torch.empty(rows, 2, dtype=torch.float32, device=q.device)
+    else:
+        o_part, ml_part = workspace[0], workspace[1]
+        assert o_part.numel() >= rows * D and ml_part.numel() >= rows * 2, \
+            "append workspace too small"
+    lib, hip = _lib()
+    out = torch.empty(T, Hq, D, dtype=q.dtype, device=q.device)
+    rc = lib.oa_attention_append(
+        hip.current_stream_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+        block_table.data_ptr(), seq_lens.data_ptr(), cu_q.data_ptr(),
+        o_part.data_ptr(), ml_part.data_ptr(), out.data_ptr(), B, T, Hq, Hk, D,
+        block_table.shape[1], block_size, nsplit, scale, q.stride(0), max_q,
+    )
+    hip.check(rc, "oa_attention_append")
+    return out
+
+
 def _bf16_prenorm() -> bool:
     """OPSAGENT_BF16_PRENORM=1: at M=1 run rmsnorm as its own pass and the
     PLAIN bf16 gemv (A/B knob mirroring the fp8 M=1 prenorm win)."""

@@ -22,6 +22,7 @@ SOURCES = [
     "elementwise.hip",
     "sampling.hip",
     "attention_decode.hip",
+    "attention_append.hip",
     "attention_prefill.hip",
     "fp8_moe.hip",
     "moe_gemv.hip",

@@ -62,6 +62,12 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.oa_attention_prefill.restype = i
     lib.oa_attention_decode.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, f, i, i]
     lib.oa_attention_decode.restype = i
+    lib.oa_attention_append.argtypes = [
+        p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, f, i, i,
+    ]
+    lib.oa_attention_append.restype = i
+    lib.oa_attention_append_max_q.argtypes = [i]
+    lib.oa_attention_append_max_q.restype = i
     lib.oa_attention_decode_rope.argtypes = [
         p, p, p, p, p, p, p, p, p, p, p, p, p, p,
         i, i, i, i, i, i, i, f, i, i, i,

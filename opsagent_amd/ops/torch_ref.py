@@ -135,6 +135,36 @@ def attention_decode_paged(
     return torch.stack(outs).to(q.dtype)
 
 
+def attention_append_paged(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    block_table: torch.Tensor,
+    seq_lens: torch.Tensor,
+    cu_q: torch.Tensor,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """Append attention: sequence b has L_b = cu_q[b+1]-cu_q[b] new query
+    tokens whose K/V are already in the cache; seq_lens[b] counts all keys
+    including them. Token j is decode attention at length seq_lens[b]-L_b+j+1.
+
+    q: [T, Hq, D]; returns [T, Hq, D].
+    """
+    B = seq_lens.shape[0]
+    outs = []
+    for b in range(B):
+        t0, t1 = int(cu_q[b].item()), int(cu_q[b + 1].item())
+        n, L = int(seq_lens[b].item()), t1 - t0
+        for j in range(L):
+            length = torch.tensor([n - L + j + 1], dtype=seq_lens.dtype, device=seq_lens.device)
+            outs.append(
+                attention_decode_paged(
+                    q[t0 + j : t0 + j + 1], k_cache, v_cache, block_table[b : b + 1], length, scale
+                )
+            )
+    return torch.cat(outs, dim=0)
+
+
 def kv_cache_write(
     k_cache: torch.Tensor,
     v_cache: torch.Tensor,
