@@ -321,10 +321,15 @@ class LLMEngine:
                             dtype=torch.float32, device=dev),
                 torch.empty(self.max_batch * hk_local * ns, G, 2,
                             dtype=torch.float32, device=dev),
-                torch.empty(self.max_batch * hk_local, dtype=torch.int32, device=dev),
+                # ticket words of the in-launch combine: zeroed here, once;
+                # every launch hands them back zeroed
+                torch.zeros(self.max_batch * hk_local, dtype=torch.int32, device=dev),
             )
         else:
             self._dec_ws = None
+        # decode steps of at most this many rows fold the split combine into
+        # the attention launch (0: never; see profiles/README.md for the A/B)
+        self._dec_fused_max_b = int(os.environ.get("OPSAGENT_DECODE_FUSED_MAX_B", "0"))
 
         # append attention: catch-up and verify passes (a few new tokens of
         # a sequence against its cached past) read the paged cache in place
@@ -1126,6 +1131,7 @@ class LLMEngine:
             seq_lens=self._dec_seq_lens[:B],
             decode_workspace=self._dec_ws,
             nsplit=self._dec_nsplit,
+            fused_combine=self._dec_ws is not None and B <= self._dec_fused_max_b,
         )
 
     def _decode_eager(self, B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu):

@@ -71,6 +71,9 @@ class ForwardBatch:
     seq_lens: Optional[torch.Tensor] = None     # [B] int32
     decode_workspace: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
     nsplit: Optional[int] = None
+    # decode: fold the split combine into the attention launch (needs the
+    # three-tensor workspace with zeroed ticket words)
+    fused_combine: bool = False
     # fp8 KV prefill: int32 slots of every key (past + new), made once per
     # step by gather_slots() and shared by all layers
     gather_slots_i32: Optional[torch.Tensor] = None
@@ -174,6 +177,7 @@ class Attention(nn.Module):
                 q, k, v, k_cache, v_cache, fb.block_table, fb.seq_lens,
                 cos, sin, fb.slot_mapping, scale=self.scale,
                 workspace=fb.decode_workspace, nsplit=fb.nsplit,
+                fused_combine=fb.fused_combine,
             ).view(T, self.hq * self.hd)
             out = self._o(out)
             return tp_all_reduce(out)
@@ -328,6 +332,7 @@ class DecoderLayer(nn.Module):
                 q, k, v, k_cache, v_cache, fb.block_table, fb.seq_lens,
                 cos, sin, fb.slot_mapping, scale=at.scale,
                 workspace=fb.decode_workspace, nsplit=fb.nsplit,
+                fused_combine=fb.fused_combine,
             ).view(T, at.hq * at.hd)
         else:
             q, k, v = ops.rope_kv_fused(

@@ -685,11 +685,11 @@ def attention_decode_paged(
     """q [B, Hq, D]; caches [num_blocks, block_size, Hk, D]; out [B, Hq, D].
 
     fused_combine folds the split reduction into the attention launch via the
-    in-launch G16 release/acquire hand-off (one kernel + a memset node
-    instead of two kernels per layer). Measured on MI355X it is ~0.4 ms/step
-    SLOWER than the two-kernel form at 8B decode (the single last-arriving
-    block serializes a reduction the combine kernel spreads over B*Hq blocks)
-    — kept as a correct, tested option; default off."""
+    in-launch release/acquire hand-off (one kernel + a memset node instead
+    of two kernels per layer; this entry clears the ticket words itself on
+    every call). The output is bit-identical to the two-kernel form. The
+    engine's decode path is attention_decode_rope; see profiles/README.md
+    for what the in-launch combine measured there."""
     if not _is_gpu(q):
         return torch_ref.attention_decode_paged(q, k_cache, v_cache, block_table, seq_lens, scale)
     assert q.dtype == torch.bfloat16
@@ -952,13 +952,20 @@ def attention_decode_rope(
     scale: Optional[float] = None,
     workspace: Optional[Tuple[torch.Tensor, ...]] = None,
     nsplit: Optional[int] = None,
+    fused_combine: bool = False,
 ) -> torch.Tensor:
     """Fully-fused decode attention: RoPE(q, k) + paged-KV scatter + split-K
     attention + combine in two launches, replacing the separate rope_kv
     launch per layer. q [B, Hq, D], k/v [B, Hk, D] are the RAW (un-roped)
     GEMV outputs (head-slice views of the fused qkv buffer are fine —
     per-tensor token strides); slots [B] int32 gives the new token's cache
-    slot. CPU path: rope_kv then the torch reference attention."""
+    slot. CPU path: rope_kv then the torch reference attention.
+
+    fused_combine folds the split reduction into the attention launch (one
+    launch, no memset node; bit-identical output). It needs the three-tensor
+    workspace (o_part, ml_part, tickets): B*Hk int32 ticket words that were
+    ZEROED when allocated — every launch leaves them zero again, so launches
+    that share a workspace on one stream need no further clearing."""
     if not _is_gpu(q):
         positions = (seq_lens.to(torch.int64) - 1).to(torch.int32)
         q2, k2 = torch_ref.rope_apply(q, k, cos, sin, positions)
@@ -978,13 +985,31 @@ def attention_decode_rope(
     scale = scale if scale is not None else D ** -0.5
     if nsplit is None:
         nsplit = decode_nsplit(B, Hk, int(block_table.shape[1] * block_size))
+    cnt_ws = None
     if workspace is None:
         o_part = torch.empty(B * Hk * nsplit, G, D, dtype=torch.float32, device=q.device)
         ml_part = torch.empty(B * Hk * nsplit, G, 2, dtype=torch.float32, device=q.device)
+        if fused_combine:
+            cnt_ws = torch.zeros(B * Hk, dtype=torch.int32, device=q.device)
     else:
         o_part, ml_part = workspace[0], workspace[1]
+        if fused_combine:
+            assert len(workspace) >= 3, "fused_combine needs (o_part, ml_part, tickets)"
+            cnt_ws = workspace[2]
+            assert cnt_ws.dtype == torch.int32 and cnt_ws.numel() >= B * Hk
     lib, hip = _lib()
     out = torch.empty(B, Hq, D, dtype=q.dtype, device=q.device)
+    if fused_combine:
+        rc = lib.oa_attention_decode_rope_fused(
+            hip.current_stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+            k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
+            seq_lens.data_ptr(), cos.data_ptr(), sin.data_ptr(), slots.data_ptr(),
+            o_part.data_ptr(), ml_part.data_ptr(), cnt_ws.data_ptr(), out.data_ptr(),
+            B, Hq, Hk, D, block_table.shape[1], block_size, nsplit, scale,
+            q.stride(0), k.stride(0), v.stride(0),
+        )
+        hip.check(rc, "oa_attention_decode_rope_fused")
+        return out
     rc = lib.oa_attention_decode_rope(
         hip.current_stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
         k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),

@@ -73,6 +73,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         i, i, i, i, i, i, i, f, i, i, i,
     ]
     lib.oa_attention_decode_rope.restype = i
+    lib.oa_attention_decode_rope_fused.argtypes = [
+        p, p, p, p, p, p, p, p, p, p, p, p, p, p, p,
+        i, i, i, i, i, i, i, f, i, i, i,
+    ]
+    lib.oa_attention_decode_rope_fused.restype = i
     # fp8 paged KV cache (kv_fp8.hip)
     lib.oa_rope_kv_fp8.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i]
     lib.oa_rope_kv_fp8.restype = i
