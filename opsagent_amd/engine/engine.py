@@ -342,9 +342,18 @@ class LLMEngine:
             aa = os.environ.get("OPSAGENT_APPEND_ATTN", "") == "1"
         self.append_attention = bool(aa)
         self._append_cap = ops.append_max_q(G)
-        if self.append_attention and self.kv_cache_dtype == "fp8":
-            log.warning("append_attention is ignored with kv_cache_dtype fp8")
-            self.append_attention = False
+        # An fp8 cache has a key of its own, append_attention_fp8 (the append
+        # kernel reading codes and scales in place); append_attention alone
+        # stays off there. With a bf16 cache the fp8 key has no effect.
+        aa8 = cfg.get("append_attention_fp8")
+        if aa8 is None:
+            aa8 = os.environ.get("OPSAGENT_APPEND_ATTN_FP8", "") == "1"
+        if self.kv_cache_dtype == "fp8":
+            if aa8:
+                self.append_attention = True
+            elif self.append_attention:
+                log.warning("append_attention is ignored with kv_cache_dtype fp8")
+                self.append_attention = False
         if self.append_attention and (
             self._append_cap < 1
             or (self.device == "cuda" and self.spec.head_dim != 128)

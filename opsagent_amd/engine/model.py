@@ -241,6 +241,12 @@ class Attention(nn.Module):
                 q.unsqueeze(0), k_full.unsqueeze(0), v_full.unsqueeze(0),
                 scale=self.scale,
             )
+        if fb.kind == "append":
+            return ops.attention_append_paged_fp8(
+                q, k_codes, v_codes, k_scale, v_scale, fb.block_table,
+                fb.seq_lens, fb.cu_q, fb.max_q, scale=self.scale,
+                workspace=fb.decode_workspace, nsplit=fb.nsplit,
+            )
         return ops.attention_decode_paged_fp8(
             q, k_codes, v_codes, k_scale, v_scale, fb.block_table, fb.seq_lens,
             scale=self.scale, workspace=fb.decode_workspace, nsplit=fb.nsplit,

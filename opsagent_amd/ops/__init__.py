@@ -31,6 +31,7 @@ __all__ = [
     "rope_kv_fused_fp8",
     "kv_gather_fp8",
     "attention_decode_paged_fp8",
+    "attention_append_paged_fp8",
     "greedy_sample_masked",
     "rope_cos_sin",
 ]
@@ -826,6 +827,68 @@ def attention_append_paged(
         block_table.shape[1], block_size, nsplit, scale, q.stride(0), max_q,
     )
     hip.check(rc, "oa_attention_append")
+    return out
+
+
+def attention_append_paged_fp8(
+    q: torch.Tensor,
+    k_codes: torch.Tensor,
+    v_codes: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    block_table: torch.Tensor,
+    seq_lens: torch.Tensor,
+    cu_q: torch.Tensor,
+    max_q: int,
+    scale: Optional[float] = None,
+    workspace: Optional[Tuple[torch.Tensor, ...]] = None,
+    nsplit: Optional[int] = None,
+) -> torch.Tensor:
+    """attention_append_paged over the fp8 paged cache, read in place: codes
+    uint8 [num_blocks, block_size, Hk, 128], scales f32 [num_blocks,
+    block_size, Hk]. q stays bf16; the codes feed the MFMAs as exact bf16,
+    k_scale multiplies the fp32 score and v_scale the fp32 probability.
+    append_max_q, append_partition and append_workspace describe it as they
+    do the bf16 kernel. out [T, Hq, 128] bf16."""
+    if not _is_gpu(q):
+        return torch_ref.attention_append_paged_fp8(
+            q, k_codes, v_codes, k_scale, v_scale, block_table, seq_lens, cu_q, scale
+        )
+    assert q.dtype == torch.bfloat16
+    assert q.stride(2) == 1 and q.stride(1) == q.shape[2], "q heads must be inner-contiguous"
+    assert block_table.dtype == torch.int32 and seq_lens.dtype == torch.int32
+    assert cu_q.dtype == torch.int32 and cu_q.is_contiguous()
+    assert block_table.is_contiguous()
+    assert k_codes.dtype == torch.uint8 and k_codes.is_contiguous()
+    assert v_codes.dtype == torch.uint8 and v_codes.is_contiguous()
+    assert k_scale.dtype == torch.float32 and k_scale.is_contiguous()
+    assert v_scale.dtype == torch.float32 and v_scale.is_contiguous()
+    T, Hq, D = q.shape
+    B = seq_lens.shape[0]
+    assert cu_q.shape[0] == B + 1
+    nb, block_size, Hk, _ = k_codes.shape
+    G = Hq // Hk
+    scale = scale if scale is not None else D ** -0.5
+    if nsplit is None:
+        nsplit = decode_nsplit(B, Hk, int(block_table.shape[1] * block_size))
+    rows = B * Hk * nsplit * max_q * G
+    if workspace is None:
+        o_part = torch.empty(rows, D, dtype=torch.float32, device=q.device)
+        ml_part = torch.empty(rows, 2, dtype=torch.float32, device=q.device)
+    else:
+        o_part, ml_part = workspace[0], workspace[1]
+        assert o_part.numel() >= rows * D and ml_part.numel() >= rows * 2, \
+            "append workspace too small"
+    lib, hip = _lib()
+    out = torch.empty(T, Hq, D, dtype=q.dtype, device=q.device)
+    rc = lib.oa_attention_append_fp8(
+        hip.current_stream_ptr(), q.data_ptr(), k_codes.data_ptr(),
+        v_codes.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+        block_table.data_ptr(), seq_lens.data_ptr(), cu_q.data_ptr(),
+        o_part.data_ptr(), ml_part.data_ptr(), out.data_ptr(), B, T, Hq, Hk, D,
+        block_table.shape[1], block_size, nsplit, scale, q.stride(0), max_q,
+    )
+    hip.check(rc, "oa_attention_append_fp8")
     return out
 
 

@@ -35,6 +35,19 @@
 // row tiles (wave w owns tiles w, w+4; all waves walk every key, so K/V come
 // from HBM once and from L2 after). Wave-private V images mean the main loop
 // has no block barrier.
+//
+// fp8 cache (FP8 = true, the layout of kv_fp8.hip): kc/vc are e4m3 codes
+// uint8 [num_slots, Hk, 128] with one f32 scale per (slot, kv-head) row. The
+// codes become bf16 EXACTLY (every e4m3 value is a bf16 value) and feed the
+// MFMAs unscaled; the scales fold in fp32 on the other side of each product:
+//   score = (K_codes · q) * k_scale[key]          before the scale*log2e fold
+//   O    += V_codes^T · bf16(p * v_scale[key])    one rounding; l keeps p
+// A lane's eight scores and eight P values of a step belong to the same keys
+// kb0 + 16t + 4fs + r, so one 4-B load per lane per step (k_scale of key
+// kb0 + lane in the lower half-wave, v_scale of key kb0 + lane - 32 in the
+// upper) fetches every scale the wave needs; a 256-B wave-private LDS strip
+// hands them out as four b128 reads. Everything else — partition, masks,
+// softmax, P·V, merges, combine — is the one code path.
 
 #include "common.h"
 
@@ -45,6 +58,7 @@ typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4v;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v_t;
 
 // byte offset of 16-byte chunk ch (0..15) of row `row` in a [32][128] bf16
 // image with 256-B rows; the XOR serves the b128 writes and the tr reads
@@ -69,10 +83,42 @@ __device__ __forceinline__ size_t append_slot(int key, int last_key, int block_s
     return ((size_t)entry << block_shift) | (size_t)(kk & bmask);
 }
 
-template <int NRT, bool SMALLBS>
+// two e4m3 codes (byte pair `HI` of w) -> two bf16, exact (every e4m3 value
+// is a bf16 value): one v_cvt_scalef32_pk_bf16_fp8 with the scale 1.0. It
+// gives the bits of v_cvt_pk_f32_fp8 followed by the high halves of the two
+// f32 (three instructions; measured 5-10 % slower on the row-tile shapes);
+// the `codes_all` parity case covers every non-NaN code.
+template <bool HI>
+__device__ __forceinline__ uint32_t fp8x2_to_bf16x2(uint32_t w) {
+    const bf16x2v_t b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI);
+    return __builtin_bit_cast(uint32_t, b);
+}
+
+// 8 e4m3 codes (element-linear bytes) -> 8 bf16 in element order
+__device__ __forceinline__ u32x4_t fp8x8_to_bf16x8(const uint2& w) {
+    u32x4_t o;
+    o[0] = fp8x2_to_bf16x2<false>(w.x);
+    o[1] = fp8x2_to_bf16x2<true>(w.x);
+    o[2] = fp8x2_to_bf16x2<false>(w.y);
+    o[3] = fp8x2_to_bf16x2<true>(w.y);
+    return o;
+}
+
+// what a lane holds of the step ahead: K fragments and V image rows as loaded
+template <bool FP8> struct AppendRaw {
+    typedef bf16x8_t k_t;
+    typedef u32x4_t v_t;
+};
+template <> struct AppendRaw<true> {
+    typedef uint2 k_t;
+    typedef uint2 v_t;
+};
+
+template <int NRT, bool SMALLBS, bool FP8>
 __global__ __launch_bounds__(256) void append_attn_kernel(
-    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
-    const uint16_t* __restrict__ vc, const int* __restrict__ block_table,
+    const uint16_t* __restrict__ q, const void* __restrict__ kcv,
+    const void* __restrict__ vcv, const float* __restrict__ kscl,
+    const float* __restrict__ vscl, const int* __restrict__ block_table,
     const int* __restrict__ seq_lens, const int* __restrict__ cu_q,
     float* __restrict__ o_part, float* __restrict__ ml_part, int Hk,
     int gshift /* log2(G) */, int max_blocks, int block_shift, int nsplit,
@@ -83,6 +129,14 @@ __global__ __launch_bounds__(256) void append_attn_kernel(
     constexpr int SMEM = MO_BYTES > 4 * V_BYTES ? MO_BYTES : 4 * V_BYTES;
     __shared__ __attribute__((aligned(16))) char smem[SMEM];
     __shared__ float s_ml[4][ROWS][2];
+    // fp8 only: per wave, k_scale of the step's 32 keys then their v_scale
+    __shared__ __attribute__((aligned(16))) float s_scl[FP8 ? 4 * 64 : 1];
+    typedef typename AppendRaw<FP8>::k_t kraw_t;
+    typedef typename AppendRaw<FP8>::v_t vraw_t;
+    const uint16_t* kc = reinterpret_cast<const uint16_t*>(kcv);
+    const uint16_t* vc = reinterpret_cast<const uint16_t*>(vcv);
+    const uint8_t* kc8 = reinterpret_cast<const uint8_t*>(kcv);
+    const uint8_t* vc8 = reinterpret_cast<const uint8_t*>(vcv);
 
     const int bh = blockIdx.x;
     const int b = bh / Hk;
@@ -183,29 +237,47 @@ __global__ __launch_bounds__(256) void append_attn_kernel(
 #define SLOT_OF(KEY)                                                              \
     append_slot<SMALLBS>((KEY), last_key, block_shift, bmask, btrow, max_blocks,  \
                          e_b0, e_e0, e_e1, e_e2)
-    // K A-fragments: key kb0 + 16t + fr, dims 32s + 8fs .. +7
+    // K A-fragments: key kb0 + 16t + fr, dims 32s + 8fs .. +7 (fp8: the
+    // same elements as 8 B of codes)
 #define LOAD_K(KB0)                                                               \
     _Pragma("unroll") for (int t = 0; t < 2; ++t) {                               \
-        const uint16_t* kp =                                                      \
-            kc + (SLOT_OF((KB0) + 16 * t + fr) * Hk + h) * DHEAD + fs * 8;        \
-        _Pragma("unroll") for (int s = 0; s < 4; ++s) ak[t][s] =                  \
-            *reinterpret_cast<const bf16x8_t*>(kp + s * 32);                      \
+        const size_t ke =                                                         \
+            (SLOT_OF((KB0) + 16 * t + fr) * Hk + h) * DHEAD + fs * 8;             \
+        _Pragma("unroll") for (int s = 0; s < 4; ++s) {                           \
+            if constexpr (FP8)                                                    \
+                ak[t][s] = *reinterpret_cast<const kraw_t*>(kc8 + ke + s * 32);   \
+            else                                                                  \
+                ak[t][s] = *reinterpret_cast<const kraw_t*>(kc + ke + s * 32);    \
+        }                                                                         \
     }
     // V rows for the LDS image: key kb0 + 4i + fs, chunk fr
 #define LOAD_V(KB0)                                                               \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i) vv[i] =                         \
-        *reinterpret_cast<const u32x4_t*>(                                        \
-            vc + (SLOT_OF((KB0) + 4 * i + fs) * Hk + h) * DHEAD + fr * 8);
+    _Pragma("unroll") for (int i = 0; i < 8; ++i) {                               \
+        const size_t ve =                                                         \
+            (SLOT_OF((KB0) + 4 * i + fs) * Hk + h) * DHEAD + fr * 8;              \
+        if constexpr (FP8)                                                        \
+            vv[i] = *reinterpret_cast<const vraw_t*>(vc8 + ve);                   \
+        else                                                                      \
+            vv[i] = *reinterpret_cast<const vraw_t*>(vc + ve);                    \
+    }
+    // fp8 scales of the step: lane l < 32 takes k_scale of key kb0 + l, lane
+    // l >= 32 v_scale of key kb0 + l - 32, clamped like every other load
+#define LOAD_SC(KB0)                                                              \
+    if constexpr (FP8)                                                            \
+        sraw = (lane < 32 ? kscl : vscl)[SLOT_OF((KB0) + (lane & 31)) * Hk + h];
 
     // One step ahead: step i's K and V are in registers when it starts.
     // V(i) goes to the LDS image and V(i+1) is requested at once; K(i+1)
     // is requested as soon as the S^T MFMAs have read K(i), so both stream
     // under the softmax and P·V of step i. The look-ahead loads are
     // unconditional: past the range they clamp to the last valid key.
-    bf16x8_t ak[2][4] = {};
-    u32x4_t vv[8] = {};
+    kraw_t ak[2][4] = {};
+    vraw_t vv[8] = {};
+    float sraw = 0.0f;
+    float* sstrip = s_scl + (FP8 ? wid * 64 : 0);
     LOAD_ENT(wstart);
     LOAD_V(wstart)
+    LOAD_SC(wstart)
     LOAD_K(wstart)
     LOAD_ENT(wstart + 32);
 
@@ -214,29 +286,68 @@ __global__ __launch_bounds__(256) void append_attn_kernel(
         // these writes land after the previous step's tr reads and before
         // this step's; the image is wave-private, no barrier is needed.
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            *reinterpret_cast<u32x4_t*>(vbuf + v_img_off(4 * i + fs, fr)) = vv[i];
+        for (int i = 0; i < 8; ++i) {
+            u32x4_t vrow;
+            if constexpr (FP8) vrow = fp8x8_to_bf16x8(vv[i]);
+            else vrow = vv[i];
+            *reinterpret_cast<u32x4_t*>(vbuf + v_img_off(4 * i + fs, fr)) = vrow;
+        }
+        // the scale strip follows the same rule: this write lands after the
+        // previous step's reads of it and before this step's
+        if constexpr (FP8) sstrip[lane] = sraw;
         LOAD_V(kb0 + 32)
+        LOAD_SC(kb0 + 32)
 
         const bool need_mask = (kb0 + 32 > wend) || (kb0 + 32 > all_visible_end);
 
         // ---- S^T = K · Q^T ------------------------------------------------
         f32x4_t sall[NRT][2];
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) {
-            if (tile0 + rt * tstep >= ntile) continue;  // wave-uniform
+        if constexpr (FP8) {
+            // codes -> exact bf16 once per step, shared by the row tiles
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                f32x4_t a = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+                bf16x8_t akb[4];
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        ak[t][s], *reinterpret_cast<bf16x8_t*>(&bq[rt][s]), a, 0, 0, 0);
-                sall[rt][t] = a;
+                    akb[s] = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16x8(ak[t][s]));
+#pragma unroll
+                for (int rt = 0; rt < NRT; ++rt) {
+                    if (tile0 + rt * tstep >= ntile) continue;  // wave-uniform
+                    f32x4_t a = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            akb[s], *reinterpret_cast<bf16x8_t*>(&bq[rt][s]), a, 0, 0, 0);
+                    sall[rt][t] = a;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) {
+                if (tile0 + rt * tstep >= ntile) continue;  // wave-uniform
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    f32x4_t a = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            ak[t][s], *reinterpret_cast<bf16x8_t*>(&bq[rt][s]), a, 0, 0, 0);
+                    sall[rt][t] = a;
+                }
             }
         }
         LOAD_K(kb0 + 32)
         LOAD_ENT(kb0 + 64);
+
+        // fp8: k_scale / v_scale of the lane's keys kb0 + 16t + 4fs + r
+        f32x4_t ksc[2], vsc[2];
+        if constexpr (FP8) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                ksc[t] = *reinterpret_cast<const f32x4_t*>(sstrip + 16 * t + 4 * fs);
+                vsc[t] = *reinterpret_cast<const f32x4_t*>(sstrip + 32 + 16 * t + 4 * fs);
+            }
+        }
 
         // ---- mask, online softmax -----------------------------------------
         union PF {
@@ -247,6 +358,10 @@ __global__ __launch_bounds__(256) void append_attn_kernel(
         for (int rt = 0; rt < NRT; ++rt) {
             if (tile0 + rt * tstep >= ntile) continue;  // wave-uniform
             f32x4_t st[2] = {sall[rt][0], sall[rt][1]};
+            if constexpr (FP8) {
+                st[0] *= ksc[0];
+                st[1] *= ksc[1];
+            }
             // lane's score st[t][r] is key kb0 + 16t + 4fs + r of its row
             if (need_mask) {
                 const int lim = min(wend - 1, plim[rt]);
@@ -281,6 +396,13 @@ __global__ __launch_bounds__(256) void append_attn_kernel(
             for (int db = 0; db < 8; ++db)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[rt][db][r] *= alpha;
+            // fp8: v_scale rides on P in fp32, one rounding; l kept p itself
+            if constexpr (FP8) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) p[t][r] *= vsc[t][r];
+            }
             // P^T B-fragment: k = 8fs + j <-> key (j<4 ? 4fs+j : 16+4fs+j-4)
             pf[rt].u[0] = pack_bf16x2(p[0][0], p[0][1]);
             pf[rt].u[1] = pack_bf16x2(p[0][2], p[0][3]);
@@ -319,6 +441,7 @@ __global__ __launch_bounds__(256) void append_attn_kernel(
 #undef SLOT_OF
 #undef LOAD_K
 #undef LOAD_V
+#undef LOAD_SC
 
     // the four groups hold the same m and disjoint key sums
 #pragma unroll
@@ -436,13 +559,14 @@ extern "C" int oa_attention_append_max_q(int G) {
     return (G == 1 || G == 2 || G == 4 || G == 8) ? APPEND_MAX_Q : 0;
 }
 
-extern "C" int oa_attention_append(void* stream, const void* q, const void* kc,
-                                   const void* vc, const void* block_table,
-                                   const void* seq_lens, const void* cu_q,
-                                   void* o_part, void* ml_part, void* out, int B,
-                                   int T, int Hq, int Hk, int D, int max_blocks,
-                                   int block_size, int nsplit, float scale,
-                                   int q_stride, int max_q) {
+// One launcher for both cache formats; the bf16 entry passes no scales.
+static int append_launch(void* stream, const void* q, const void* kc,
+                         const void* vc, const void* kscl, const void* vscl,
+                         const void* block_table, const void* seq_lens,
+                         const void* cu_q, void* o_part, void* ml_part, void* out,
+                         int B, int T, int Hq, int Hk, int D, int max_blocks,
+                         int block_size, int nsplit, float scale, int q_stride,
+                         int max_q, bool fp8) {
     if (q_stride % 8 != 0) return -103;
     if (D != DHEAD) return -100;
     if ((block_size & (block_size - 1)) != 0) return -101;
@@ -458,20 +582,25 @@ extern "C" int oa_attention_append(void* stream, const void* q, const void* kc,
     const int rmax = max_q * G;
     const float scale2 = scale * 1.4426950408889634f;
     dim3 grid(B * Hk, nsplit), block(256);
-#define LAUNCH_A(NRTV, SB)                                                      \
-    hipLaunchKernelGGL((append_attn_kernel<NRTV, SB>), grid, block, 0,          \
-                       (hipStream_t)stream, (const uint16_t*)q,                 \
-                       (const uint16_t*)kc, (const uint16_t*)vc,                \
+#define LAUNCH_A(NRTV, SB, F8)                                                  \
+    hipLaunchKernelGGL((append_attn_kernel<NRTV, SB, F8>), grid, block, 0,      \
+                       (hipStream_t)stream, (const uint16_t*)q, kc, vc,         \
+                       (const float*)kscl, (const float*)vscl,                  \
                        (const int*)block_table, (const int*)seq_lens,           \
                        (const int*)cu_q, (float*)o_part, (float*)ml_part, Hk,   \
                        gshift, max_blocks, block_shift, nsplit, scale2,         \
                        q_stride, rmax)
+#define LAUNCH_F(NRTV, SB)                                                      \
+    do {                                                                        \
+        if (fp8) LAUNCH_A(NRTV, SB, true); else LAUNCH_A(NRTV, SB, false);      \
+    } while (0)
     const bool smallbs = block_size < 16;  // per-lane block-table loads
     if (rmax <= 16) {
-        if (smallbs) LAUNCH_A(1, true); else LAUNCH_A(1, false);
+        if (smallbs) LAUNCH_F(1, true); else LAUNCH_F(1, false);
     } else {
-        if (smallbs) LAUNCH_A(2, true); else LAUNCH_A(2, false);
+        if (smallbs) LAUNCH_F(2, true); else LAUNCH_F(2, false);
     }
+#undef LAUNCH_F
 #undef LAUNCH_A
     HIP_CHECK_LAUNCH();
     hipLaunchKernelGGL(append_combine_kernel, dim3(T * Hq), dim3(128), 0,
@@ -480,4 +609,31 @@ extern "C" int oa_attention_append(void* stream, const void* q, const void* kc,
                        B, Hk, gshift, nsplit, rmax);
     HIP_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int oa_attention_append(void* stream, const void* q, const void* kc,
+                                   const void* vc, const void* block_table,
+                                   const void* seq_lens, const void* cu_q,
+                                   void* o_part, void* ml_part, void* out, int B,
+                                   int T, int Hq, int Hk, int D, int max_blocks,
+                                   int block_size, int nsplit, float scale,
+                                   int q_stride, int max_q) {
+    return append_launch(stream, q, kc, vc, nullptr, nullptr, block_table,
+                         seq_lens, cu_q, o_part, ml_part, out, B, T, Hq, Hk, D,
+                         max_blocks, block_size, nsplit, scale, q_stride, max_q,
+                         false);
+}
+
+// The same kernel over the fp8 paged cache: kc/vc are e4m3 codes uint8
+// [blocks, block_size, Hk, 128], k_scale/v_scale f32 [blocks, block_size, Hk].
+extern "C" int oa_attention_append_fp8(
+    void* stream, const void* q, const void* kc, const void* vc,
+    const void* k_scale, const void* v_scale, const void* block_table,
+    const void* seq_lens, const void* cu_q, void* o_part, void* ml_part,
+    void* out, int B, int T, int Hq, int Hk, int D, int max_blocks,
+    int block_size, int nsplit, float scale, int q_stride, int max_q) {
+    return append_launch(stream, q, kc, vc, k_scale, v_scale, block_table,
+                         seq_lens, cu_q, o_part, ml_part, out, B, T, Hq, Hk, D,
+                         max_blocks, block_size, nsplit, scale, q_stride, max_q,
+                         true);
 }

@@ -66,6 +66,10 @@ def _declare(lib: ctypes.CDLL) -> None:
         p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, f, i, i,
     ]
     lib.oa_attention_append.restype = i
+    lib.oa_attention_append_fp8.argtypes = [
+        p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, f, i, i,
+    ]
+    lib.oa_attention_append_fp8.restype = i
     lib.oa_attention_append_max_q.argtypes = [i]
     lib.oa_attention_append_max_q.restype = i
     lib.oa_attention_decode_rope.argtypes = [

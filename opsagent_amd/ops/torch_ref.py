@@ -261,6 +261,24 @@ def attention_decode_paged_fp8(
     return attention_decode_paged(q, kc, vc, block_table, seq_lens, scale)
 
 
+def attention_append_paged_fp8(
+    q: torch.Tensor,
+    k_codes: torch.Tensor,
+    v_codes: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    block_table: torch.Tensor,
+    seq_lens: torch.Tensor,
+    cu_q: torch.Tensor,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """Append attention over the fp8 paged cache: dequantise, then the
+    reference append attention."""
+    kc = dequant_fp8(k_codes, k_scale)
+    vc = dequant_fp8(v_codes, v_scale)
+    return attention_append_paged(q, kc, vc, block_table, seq_lens, cu_q, scale)
+
+
 def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor) -> torch.Tensor:
     w = dequant_fp8(w8, w_scale)
     return torch.nn.functional.linear(x.float(), w).to(x.dtype)
