@@ -364,7 +364,23 @@ class LLMEngine:
             )
             self.append_attention = False
         self._append_ws: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        # decode graphs end at the final norm: bucket -> (graph, hidden)
         self._graphs: Dict[int, Tuple[torch.cuda.CUDAGraph, torch.Tensor]] = {}
+
+        # fused decode head: a decode step of at most two all-greedy rows (no
+        # logit transform, no logprobs) takes ops.head_argmax — the lm_head
+        # GEMV over the rows the grammar mask allows, with the argmax in its
+        # epilogue — instead of logits + masked argmax. On by default; the
+        # environment variable applies only when the config key is absent.
+        fh = cfg.get("fused_head")
+        if fh is None:
+            fh = os.environ.get("OPSAGENT_FUSED_HEAD", "1") != "0"
+        self.fused_head = bool(fh)
+        self._vocab_bits = (1 << self.spec.vocab_size) - 1
+        # device copy of the step's grammar mask, filled behind the layers
+        self._dec_mask = torch.empty(
+            self.max_batch, words_pin, dtype=torch.int32, device=dev
+        )
 
         self.requests: Dict[int, Request] = {}
         self.waiting: List[Request] = []
@@ -1096,15 +1112,35 @@ class LLMEngine:
             bt_cpu[i, :nb] = torch.tensor(seq.blocks, dtype=torch.int32)
 
         if self.device == "cuda" and self.use_hipgraph:
-            logits = self._decode_graphed(B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu)
+            hidden = self._decode_hidden_graphed(
+                B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu
+            )
         else:
-            logits = self._decode_eager(B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu)
+            hidden = self._decode_hidden_eager(
+                B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu
+            )
+
+        # The head runs behind the layers, outside the graph: the grammar mask
+        # depends only on tokens already accepted, so it is filled and copied
+        # while the GPU is still inside the layers, and the head that follows
+        # on the same stream can skip every vocabulary row the mask rules out.
+        mask_t = self._stage_mask(batch)
+        tokens = None
+        logits = None
+        if self._fused_head_ok(batch, hidden):
+            tokens = ops.head_argmax(hidden[:B], self.model.lm_head, mask_t)
+            self.perf.record_metric(
+                "engine_head_live_rows", float(self._head_live_rows(B, mask_t is not None))
+            )
+        else:
+            # all rows of the bucket, as the graph used to compute them
+            logits = self.model.compute_logits(hidden)[:B]
 
         # this step wrote KV for each sequence's current last token
         for req in batch:
             req.seq.num_cached = len(req.seq.token_ids)
             req.seq.publish_full_blocks()
-        self._sample_and_append(batch, logits)
+        self._sample_and_append(batch, logits, mask_t=mask_t, tokens=tokens)
         self._reap()
         self.perf.record_metric("engine_decode_step_ms", (time.perf_counter() - t0) * 1000.0)
 
@@ -1143,13 +1179,17 @@ class LLMEngine:
             fused_combine=self._dec_ws is not None and B <= self._dec_fused_max_b,
         )
 
-    def _decode_eager(self, B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu):
+    def _decode_hidden_eager(self, B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu):
         self._fill_static(B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu, B)
         fb = self._make_decode_fb(B)
-        hidden = self.model(fb, self.kv.layers, self.kv.scales)
+        return self.model(fb, self.kv.layers, self.kv.scales)
+
+    def _decode_eager(self, B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu):
+        """One eager decode forward through the unfused head: logits [B, V]."""
+        hidden = self._decode_hidden_eager(B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu)
         return self.model.compute_logits(hidden)
 
-    def _decode_graphed(self, B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu):
+    def _decode_hidden_graphed(self, B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu):
         bucket = self._bucket(B)
         self._fill_static(B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu, bucket)
         if bucket not in self._graphs:
@@ -1162,14 +1202,12 @@ class LLMEngine:
                 with torch.cuda.stream(s):
                     for _ in range(2):
                         hidden = self.model(fb, self.kv.layers, self.kv.scales)
-                        logits = self.model.compute_logits(hidden)
                 torch.cuda.current_stream().wait_stream(s)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     hidden = self.model(fb, self.kv.layers, self.kv.scales)
-                    logits = self.model.compute_logits(hidden)
-                self._graphs[bucket] = (g, logits)
+                self._graphs[bucket] = (g, hidden)
                 log.info("captured decode hipGraph for batch bucket %d", bucket)
             except Exception:  # noqa: BLE001 — capture failure must not kill serving
                 log.exception(
@@ -1178,10 +1216,56 @@ class LLMEngine:
                 )
                 self.use_hipgraph = False
                 torch.cuda.synchronize()
-                return self._decode_eager(B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu)
-        g, logits = self._graphs[bucket]
+                return self._decode_hidden_eager(B, in_cpu, pos_cpu, slot_cpu, len_cpu, bt_cpu)
+        g, hidden = self._graphs[bucket]
         g.replay()
-        return logits[:B]
+        return hidden
+
+    # -- decode head -------------------------------------------------------
+    def _stage_mask(self, batch: List[Request]) -> Optional[torch.Tensor]:
+        """Fill the pinned grammar mask for a decode step and start its copy
+        into the static device buffer; None when no row is constrained."""
+        if not any(r.grammar_state is not None for r in batch):
+            return None
+        B = len(batch)
+        mask_cpu = self._h_mask[:B]
+        for i, r in enumerate(batch):
+            if r.grammar_state is not None:
+                r.grammar_state.fill_mask_into(mask_cpu[i])
+            else:
+                mask_cpu[i] = self._h_ones
+        if self.device != "cuda":
+            return mask_cpu
+        mask_t = self._dec_mask[:B]
+        mask_t.copy_(mask_cpu, non_blocking=True)
+        return mask_t
+
+    def _fused_head_ok(self, batch: List[Request], hidden: torch.Tensor) -> bool:
+        return (
+            self.fused_head
+            and self.device == "cuda"
+            and self.tp == 1
+            and len(batch) <= 2
+            and hidden.dtype == torch.bfloat16
+            and self.model.lm_head.dtype == torch.bfloat16
+            and self.model.lm_head.is_contiguous()
+            and self.spec.vocab_size % 8 == 0
+            and self.spec.hidden_size % 8 == 0
+            and not any(
+                r.params.needs_logit_transform() or r.params.logprobs for r in batch
+            )
+        )
+
+    def _head_live_rows(self, B: int, masked: bool) -> int:
+        """Vocabulary rows the fused head streams: tokens some batch row's
+        mask (just filled into the pinned buffer) allows."""
+        V = self.spec.vocab_size
+        if not masked:
+            return V
+        rows = self._h_mask[:B].numpy()
+        row = rows[0] if B == 1 else rows[0] | rows[1]
+        bits = int.from_bytes(row.tobytes(), "little")
+        return (bits & self._vocab_bits).bit_count()
 
     # -- sampling --------------------------------------------------------
     def _logprob_entry(self, row: torch.Tensor, tok: int, top_n: int) -> dict:
@@ -1320,11 +1404,28 @@ class LLMEngine:
         lf[idx] = sub
         return lf
 
-    def _sample_and_append(self, batch: List[Request], logits: torch.Tensor) -> None:
+    _MASK_UNSET = object()
+
+    def _sample_and_append(
+        self,
+        batch: List[Request],
+        logits: Optional[torch.Tensor],
+        mask_t=_MASK_UNSET,
+        tokens: Optional[torch.Tensor] = None,
+    ) -> None:
+        """Sample one token per row from `logits` and commit it. A decode step
+        passes the mask it has already staged (`mask_t`, None = unconstrained)
+        and, when the fused head picked them, the `tokens` themselves; logits
+        is None then."""
         B = len(batch)
-        assert logits.shape[0] == B
-        mask_t: Optional[torch.Tensor] = None
-        need_mask = any(r.grammar_state is not None for r in batch)
+        assert logits is None or logits.shape[0] == B
+        need_mask = (
+            mask_t is self._MASK_UNSET
+            and tokens is None
+            and any(r.grammar_state is not None for r in batch)
+        )
+        if mask_t is self._MASK_UNSET:
+            mask_t = None
         if need_mask:
             mask_cpu = self._h_mask[:B]
             for i, r in enumerate(batch):
@@ -1338,7 +1439,9 @@ class LLMEngine:
         # top-p, penalties, logit bias); untouched rows stay pure greedy so
         # the fused masked-argmax kernel consumes the raw bf16 logits
         needs = any(r.params.needs_logit_transform() for r in batch)
-        if self.device == "cuda":
+        if tokens is not None:
+            tokens = tokens.cpu()
+        elif self.device == "cuda":
             lg = logits.contiguous()
             if needs:
                 lg = (

@@ -33,6 +33,7 @@ __all__ = [
     "attention_decode_paged_fp8",
     "attention_append_paged_fp8",
     "greedy_sample_masked",
+    "head_argmax",
     "rope_cos_sin",
 ]
 
@@ -1105,4 +1106,54 @@ def greedy_sample_masked(
         out.data_ptr(), B, V,
     )
     hip.check(rc, "oa_masked_argmax")
+    return out
+
+
+def head_argmax_grid(V: int, M: int) -> int:
+    """Keys per batch row that ops.head_argmax needs in its scratch."""
+    lib, _ = _lib()
+    return int(lib.oa_head_argmax_grid(V, M))
+
+
+def head_argmax(
+    x: torch.Tensor,
+    w: torch.Tensor,
+    mask_bits: Optional[torch.Tensor],
+    out: Optional[torch.Tensor] = None,
+    ws: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Greedy decode head in one pass: argmax over the allowed tokens of
+    bf16(x @ w^T), without a logits row; W rows no batch row allows are not
+    read. Equal to greedy_sample_masked(linear(x, w), mask_bits) by
+    construction. x [M, K] bf16 with M <= 2; w [V, K] bf16; mask_bits
+    uint32-packed [M, ceil(V/32)] on GPU, bool [M, V] on CPU, or None.
+    Returns int32/int64 [M], -1 where no token is allowed. `out` (int32 [M])
+    and `ws` (int64 [M, head_argmax_grid(V, M)]) may be passed in."""
+    if not _is_gpu(x):
+        return torch_ref.head_argmax(x, w, mask_bits)
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 2
+    assert w.dtype == torch.bfloat16 and w.is_contiguous()
+    lib, hip = _lib()
+    M, K = x.shape
+    V = w.shape[0]
+    assert w.shape[1] == K
+    mask_ptr = None
+    if mask_bits is not None:
+        assert mask_bits.dtype == torch.int32 and mask_bits.is_contiguous()
+        assert mask_bits.shape == (M, (V + 31) // 32)
+        mask_ptr = mask_bits.data_ptr()
+    if out is None:
+        out = torch.empty(M, dtype=torch.int32, device=x.device)
+    if ws is None:
+        ws = torch.empty(
+            M * max(1, head_argmax_grid(V, M)), dtype=torch.int64, device=x.device
+        )
+    assert out.dtype == torch.int32 and out.numel() >= M and out.is_contiguous()
+    assert ws.dtype == torch.int64 and ws.is_contiguous()
+    assert ws.numel() >= M * head_argmax_grid(V, M)
+    rc = lib.oa_head_argmax(
+        hip.current_stream_ptr(), x.data_ptr(), w.data_ptr(), mask_ptr,
+        ws.data_ptr(), out.data_ptr(), M, V, K,
+    )
+    hip.check(rc, "oa_head_argmax")
     return out

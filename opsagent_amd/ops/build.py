@@ -17,6 +17,7 @@ OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libopsagent_kern
 SOURCES = [
     "rmsnorm.hip",
     "gemv.hip",
+    "head_argmax.hip",
     "rope.hip",
     "rope_kv.hip",
     "elementwise.hip",
@@ -50,7 +51,8 @@ def needs_rebuild() -> bool:
     if out_t == 0.0:
         return True
     deps = [os.path.join(CSRC, s) for s in SOURCES] + [
-        os.path.join(CSRC, h) for h in ("common.h", "decode_combine.h")
+        os.path.join(CSRC, h)
+        for h in ("common.h", "decode_combine.h", "gemv_tile.h", "gemv_pipe.h")
     ]
     return any(_mtime(d) > out_t for d in deps)
 

@@ -58,6 +58,13 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.oa_gemv_gateup_ku.restype = i
     lib.oa_masked_argmax.argtypes = [p, p, p, p, p, i, i]
     lib.oa_masked_argmax.restype = i
+    lib.oa_head_argmax.argtypes = [p, p, p, p, p, p, i, i, i]
+    lib.oa_head_argmax.restype = i
+    # probe/test entry: explicit K depth
+    lib.oa_head_argmax_ku.argtypes = [p, p, p, p, p, p, i, i, i, i]
+    lib.oa_head_argmax_ku.restype = i
+    lib.oa_head_argmax_grid.argtypes = [i, i]
+    lib.oa_head_argmax_grid.restype = i
     lib.oa_attention_prefill.argtypes = [p, p, p, p, p, i, i, i, i, i, i, f, i, i, i]
     lib.oa_attention_prefill.restype = i
     lib.oa_attention_decode.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, f, i, i]

@@ -290,3 +290,16 @@ def greedy_sample_masked(logits: torch.Tensor, mask: Optional[torch.Tensor]) -> 
     if mask is not None:
         lf = lf.masked_fill(~mask, float("-inf"))
     return lf.argmax(dim=-1)
+
+
+def head_argmax(
+    x: torch.Tensor, w: torch.Tensor, mask: Optional[torch.Tensor]
+) -> torch.Tensor:
+    """Greedy decode head: linear, rounded to bf16 as the logits row is, then
+    the masked greedy pick. x [M, K]; w [V, K]; mask [M, V] bool or None.
+    Returns int64 [M], -1 where no token is allowed."""
+    logits = torch.nn.functional.linear(x, w).to(torch.bfloat16)
+    tok = greedy_sample_masked(logits, mask)
+    if mask is not None:
+        tok = torch.where(mask.any(dim=-1), tok, torch.full_like(tok, -1))
+    return tok
