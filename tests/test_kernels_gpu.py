@@ -747,9 +747,11 @@ class TestPrefillV3:
 
 
 class TestBf16MfmaGemv:
-    """MFMA batched-decode bf16 GEMV (M 3..16, K <= 6144 win region). Pin
-    eligibility via shapes; references are plain fp32 matmuls (norm staged
-    in fp32 then rounded to bf16 exactly where the kernel rounds)."""
+    """MFMA batched-decode bf16 GEMV (default dispatch: M 3..8, K <= 6144;
+    the M 12 and 16 cases below go to hipBLASLt, M 9..16 on the kernel is in
+    tests/test_dense_bf16_gpu.py). Pin eligibility via shapes; references are
+    plain fp32 matmuls (norm staged in fp32 then rounded to bf16 exactly where
+    the kernel rounds)."""
 
     @pytest.mark.parametrize("M,N,K", [(3, 512, 1024), (8, 1000, 4096),
                                        (16, 544, 2048)])
