@@ -68,6 +68,11 @@ class SamplingParams:
     # declared tool names: with a TOOLCALLS grammar the name field only
     # accepts one of these (hallucinated-tool protection is structural)
     tool_names: Optional[List[str]] = None
+    # OpenAI `seed`: the sampling noise of token t at output position n is a
+    # function of (seed, n, t) alone. Honoured by the fused sampler
+    # (engine key fused_sampler); None derives one from the engine seed and
+    # the request id. The legacy path draws from torch's global generator.
+    seed: Optional[int] = None
 
     def needs_logit_transform(self) -> bool:
         return (
@@ -377,6 +382,26 @@ class LLMEngine:
             fh = os.environ.get("OPSAGENT_FUSED_HEAD", "1") != "0"
         self.fused_head = bool(fh)
         self._vocab_bits = (1 << self.spec.vocab_size) - 1
+
+        # fused sampler: a batch with any row that needs a logit transform
+        # goes to ops.sample_masked (mask, adjustments, top-k, top-p and a
+        # seeded Gumbel draw in one op) instead of _transform_logits +
+        # masked argmax. Off by default; the environment variable applies
+        # only when the config key is absent.
+        fs = cfg.get("fused_sampler")
+        if fs is None:
+            fs = os.environ.get("OPSAGENT_FUSED_SAMPLER", "") == "1"
+        self.fused_sampler = bool(fs)
+        if self.fused_sampler and self.device == "cuda":
+            V = self.spec.vocab_size
+            if V % 8 != 0 or V > ops.SAMPLE_MAX_VOCAB:
+                raise ValueError(
+                    f"fused_sampler needs a vocabulary that is a multiple of 8 and "
+                    f"at most {ops.SAMPLE_MAX_VOCAB}; {self.spec.name} has {V}"
+                )
+        # per-row parameters + CSR adjustments: one pinned buffer, one H2D copy
+        self._h_sampler = torch.empty(0, dtype=torch.int32, pin_memory=pin)
+        self._d_sampler = torch.empty(0, dtype=torch.int32, device=dev)
         # device copy of the step's grammar mask, filled behind the layers
         self._dec_mask = torch.empty(
             self.max_batch, words_pin, dtype=torch.int32, device=dev
@@ -1404,6 +1429,111 @@ class LLMEngine:
         lf[idx] = sub
         return lf
 
+    def _request_seed(self, req: Request) -> int:
+        """The request's 64-bit sampling seed: its own, or one mixed from the
+        engine seed and the request id (splitmix64 finaliser), so a replay of
+        the same request stream draws the same noise."""
+        m = (1 << 64) - 1
+        if req.params.seed is not None:
+            return int(req.params.seed) & m
+        x = (self.seed * 0x9E3779B97F4A7C15 + req.req_id) & m
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+        return x ^ (x >> 31)
+
+    @staticmethod
+    def _row_adjustments(req: Request, V: int) -> Tuple[List[int], List[float]]:
+        """Sparse additive logit adjustments of one row, sorted by token:
+        logit_bias minus the presence/frequency penalties over output_ids."""
+        p = req.params
+        d: Dict[int, float] = {}
+        if p.logit_bias:
+            for t, b in p.logit_bias.items():
+                t = int(t)
+                if 0 <= t < V:
+                    d[t] = d.get(t, 0.0) + float(b)
+        if (p.presence_penalty or p.frequency_penalty) and req.output_ids:
+            counts: Dict[int, int] = {}
+            for t in req.output_ids:
+                counts[t] = counts.get(t, 0) + 1
+            for t, c in counts.items():
+                if 0 <= t < V:
+                    d[t] = d.get(t, 0.0) - (
+                        p.frequency_penalty * c + p.presence_penalty
+                    )
+        toks = sorted(d)
+        return toks, [d[t] for t in toks]
+
+    def _fused_sample(
+        self, batch: List[Request], logits: torch.Tensor, mask_t
+    ) -> torch.Tensor:
+        """One ops.sample_masked call for the batch: greedy rows ride along
+        with inv_temp 0; step = output position, so preemption and recompute
+        leave a request's noise stream unchanged."""
+        import numpy as np
+
+        B, V = logits.shape
+        adjs = [self._row_adjustments(r, V) for r in batch]
+        nnz = sum(len(a[0]) for a in adjs)
+        # int32 words: seed 2B | step 2B | inv_temp B | top_k B | top_p B |
+        # adj_ptr B+1 | adj_tok nnz | adj_val nnz
+        n = 8 * B + 1 + 2 * nnz
+        if self._h_sampler.numel() < n:
+            cap = max(2 * n, 8 * self.max_batch + 1 + 1024)
+            self._h_sampler = torch.empty(
+                cap, dtype=torch.int32, pin_memory=self.device == "cuda"
+            )
+            self._d_sampler = torch.empty(cap, dtype=torch.int32, device=self.device)
+        host = self._h_sampler[:n]
+        h = host.numpy()
+        o_it, o_k, o_p, o_ptr = 4 * B, 5 * B, 6 * B, 7 * B
+        o_tok = o_ptr + B + 1
+        o_val = o_tok + nnz
+        seed = h[: 2 * B].view(np.uint64)
+        step = h[2 * B : 4 * B].view(np.uint64)
+        inv_temp = h[o_it:o_k].view(np.float32)
+        top_p = h[o_p:o_ptr].view(np.float32)
+        a = 0
+        for i, r in enumerate(batch):
+            p = r.params
+            seed[i] = self._request_seed(r)
+            step[i] = len(r.output_ids)
+            inv_temp[i] = 1.0 / p.temperature if p.temperature > 0 else 0.0
+            h[o_k + i] = p.top_k if 0 < p.top_k < V else 0
+            top_p[i] = p.top_p
+            h[o_ptr + i] = a
+            toks, vals = adjs[i]
+            if toks:
+                h[o_tok + a : o_tok + a + len(toks)] = toks
+                h[o_val + a : o_val + a + len(toks)].view(np.float32)[:] = vals
+                a += len(toks)
+        h[o_ptr + B] = a
+        if self.device == "cuda":
+            d = self._d_sampler[:n]
+            d.copy_(host, non_blocking=True)
+            lg = logits.contiguous()
+            if lg.dtype != torch.bfloat16:
+                lg = lg.to(torch.bfloat16)
+            mask = mask_t
+        else:
+            d = host
+            lg = logits.float()
+            mask = None
+            if mask_t is not None:
+                m = mask_t.numpy().view("uint32")
+                bits = np.unpackbits(m.view("uint8"), bitorder="little").reshape(B, -1)
+                mask = torch.from_numpy(bits[:, :V].astype(bool))
+        adj = None
+        if nnz:
+            adj = (d[o_ptr:o_tok], d[o_tok:o_val], d[o_val:n].view(torch.float32))
+        return ops.sample_masked(
+            lg, mask,
+            d[o_it:o_k].view(torch.float32), d[o_k:o_p],
+            d[o_p:o_ptr].view(torch.float32),
+            d[: 2 * B].view(torch.int64), d[2 * B : 4 * B].view(torch.int64),
+            adj=adj,
+        )
+
     _MASK_UNSET = object()
 
     def _sample_and_append(
@@ -1441,6 +1571,8 @@ class LLMEngine:
         needs = any(r.params.needs_logit_transform() for r in batch)
         if tokens is not None:
             tokens = tokens.cpu()
+        elif needs and self.fused_sampler:
+            tokens = self._fused_sample(batch, logits, mask_t).cpu()
         elif self.device == "cuda":
             lg = logits.contiguous()
             if needs:

@@ -19,6 +19,7 @@ repair in pkg/utils/json.go).
 
 from __future__ import annotations
 
+import dataclasses
 import json
 import threading
 import time
@@ -116,6 +117,7 @@ class ChatCompletionAPI:
         presence_penalty: float = 0.0,
         frequency_penalty: float = 0.0,
         logit_bias: Optional[dict] = None,
+        seed: Optional[int] = None,
     ):
         """Streaming chat completion: yields OpenAI `chat.completion.chunk`
         dicts as tokens are sampled (tool-call streaming is not offered; the
@@ -140,6 +142,7 @@ class ChatCompletionAPI:
             logit_bias=logit_bias,
             grammar=grammar,
             stop=stops or None,
+            seed=None if seed is None else int(seed),
         )
         # Holdback covers the worst case trim: the engine trims WHOLE tokens
         # when a stop matches, so up to (max stop bytes - 1) + (max token
@@ -281,6 +284,7 @@ class ChatCompletionAPI:
         logprobs: bool = False,
         top_logprobs: int = 0,
         tool_choice: Any = None,
+        seed: Optional[int] = None,
     ) -> Dict[str, Any]:
         perf = get_perf_stats()
         t0 = time.perf_counter()
@@ -319,11 +323,17 @@ class ChatCompletionAPI:
                 if grammar == GrammarMode.TOOLCALLS
                 else None
             ),
+            seed=None if seed is None else int(seed),
         )
         # concurrent callers (and the n>1 fan-out) batch together in the
         # engine loop's continuous batches
         n = max(1, int(n))
-        futs = [self.loop.submit(prompt_ids, params) for _ in range(n)]
+        if params.seed is not None and n > 1:
+            # one seed, n choices: choice i draws from seed + i
+            plist = [dataclasses.replace(params, seed=params.seed + i) for i in range(n)]
+        else:
+            plist = [params] * n
+        futs = [self.loop.submit(prompt_ids, pi) for pi in plist]
         results = [f.result() for f in futs]
         lp_contents = [getattr(f, "logprob_content", None) for f in futs]
         perf.record_metric("engine_chat_ms", (time.perf_counter() - t0) * 1000.0)

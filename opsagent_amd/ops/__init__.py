@@ -33,6 +33,9 @@ __all__ = [
     "attention_decode_paged_fp8",
     "attention_append_paged_fp8",
     "greedy_sample_masked",
+    "sample_masked",
+    "sample_ws_bytes",
+    "SAMPLE_MAX_VOCAB",
     "head_argmax",
     "rope_cos_sin",
 ]
@@ -1106,6 +1109,97 @@ def greedy_sample_masked(
         out.data_ptr(), B, V,
     )
     hip.check(rc, "oa_masked_argmax")
+    return out
+
+
+SAMPLE_MAX_VOCAB = 262144  # sample.hip keeps one LDS bitmap byte per 8 tokens
+
+
+def sample_ws_bytes(B: int, V: int) -> int:
+    """Scratch bytes the GPU path of ops.sample_masked needs for a [B, V]
+    batch: per row and chunk one partial and one 2048-bin histogram."""
+    lib, _ = _lib()
+    return int(lib.oa_sample_ws_bytes(B, V))
+
+
+def sample_masked(
+    logits: torch.Tensor,
+    mask_bits: Optional[torch.Tensor],
+    inv_temp: torch.Tensor,
+    top_k: torch.Tensor,
+    top_p: torch.Tensor,
+    seed: torch.Tensor,
+    step: torch.Tensor,
+    adj: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+    out: Optional[torch.Tensor] = None,
+    ws: Optional[torch.Tensor] = None,
+    info: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Seeded sampler in one op: grammar mask first, then sparse logit
+    adjustments, top-k, top-p and a Gumbel-max draw whose noise depends on
+    (seed, step, token) only. logits [B, V] bf16 (GPU) / any float (CPU);
+    mask_bits uint32-packed [B, ceil(V/32)] on GPU, bool [B, V] on CPU, or
+    None. Per row: inv_temp f32 (0 = greedy), top_k i32 (<= 0 off), top_p f32
+    (>= 1 off), seed and step int64 holding the u64 bits. adj = (adj_ptr i32
+    [B+1], adj_tok i32 [nnz], adj_val f32 [nnz]), tokens sorted and unique per
+    row. Returns int32/int64 [B], -1 where no finite allowed token exists.
+    `info` (int32 [B, 2]) receives the kept count and the bits of the smallest
+    kept adjusted logit. `out` (int32 [B]) and `ws` (sample_ws_bytes(B, V)
+    bytes, need not be initialised) may be passed in; with both given the call
+    allocates nothing. The GPU path needs V % 8 == 0 and V <= SAMPLE_MAX_VOCAB
+    and raises otherwise."""
+    if not _is_gpu(logits):
+        tok = torch_ref.sample_masked(
+            logits, mask_bits, inv_temp, top_k, top_p, seed, step, adj, info
+        )
+        if out is not None:
+            out[: tok.numel()].copy_(tok)
+            return out
+        return tok
+    assert logits.dtype == torch.bfloat16 and logits.is_contiguous() and logits.dim() == 2
+    lib, hip = _lib()
+    B, V = logits.shape
+    dev = logits.device
+    mask_ptr = None
+    if mask_bits is not None:
+        assert mask_bits.dtype == torch.int32 and mask_bits.is_contiguous()
+        assert mask_bits.shape == (B, (V + 31) // 32)
+        mask_ptr = mask_bits.data_ptr()
+    for t, dt in (
+        (inv_temp, torch.float32), (top_k, torch.int32), (top_p, torch.float32),
+        (seed, torch.int64), (step, torch.int64),
+    ):
+        assert t.dtype == dt and t.is_contiguous() and t.shape == (B,) and t.device == dev
+    ap = at = av = None
+    if adj is not None:
+        adj_ptr, adj_tok, adj_val = adj
+        assert adj_ptr.dtype == torch.int32 and adj_ptr.is_contiguous()
+        assert adj_ptr.shape == (B + 1,) and adj_ptr.device == dev
+        assert adj_tok.dtype == torch.int32 and adj_tok.is_contiguous()
+        assert adj_val.dtype == torch.float32 and adj_val.is_contiguous()
+        assert adj_tok.dim() == 1 and adj_tok.shape == adj_val.shape
+        assert adj_tok.device == dev and adj_val.device == dev
+        ap, at, av = adj_ptr.data_ptr(), adj_tok.data_ptr(), adj_val.data_ptr()
+    if out is None:
+        out = torch.empty(B, dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.numel() >= B and out.is_contiguous()
+    need = int(lib.oa_sample_ws_bytes(B, V))
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    assert ws.is_contiguous() and ws.device == dev
+    assert ws.numel() * ws.element_size() >= need and ws.data_ptr() % 16 == 0
+    ws_ptr = ws.data_ptr()
+    info_ptr = None
+    if info is not None:
+        assert info.dtype == torch.int32 and info.is_contiguous()
+        assert info.shape == (B, 2) and info.device == dev
+        info_ptr = info.data_ptr()
+    rc = lib.oa_sample(
+        hip.current_stream_ptr(), logits.data_ptr(), mask_ptr, inv_temp.data_ptr(),
+        top_k.data_ptr(), top_p.data_ptr(), seed.data_ptr(), step.data_ptr(),
+        ap, at, av, ws_ptr, info_ptr, out.data_ptr(), B, V,
+    )
+    hip.check(rc, "oa_sample")
     return out
 
 

@@ -22,6 +22,7 @@ SOURCES = [
     "rope_kv.hip",
     "elementwise.hip",
     "sampling.hip",
+    "sample.hip",
     "attention_decode.hip",
     "attention_append.hip",
     "attention_prefill.hip",

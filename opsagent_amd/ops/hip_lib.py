@@ -58,6 +58,10 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.oa_gemv_gateup_ku.restype = i
     lib.oa_masked_argmax.argtypes = [p, p, p, p, p, i, i]
     lib.oa_masked_argmax.restype = i
+    lib.oa_sample.argtypes = [p] * 14 + [i, i]
+    lib.oa_sample.restype = i
+    lib.oa_sample_ws_bytes.argtypes = [i, i]
+    lib.oa_sample_ws_bytes.restype = ctypes.c_longlong
     lib.oa_head_argmax.argtypes = [p, p, p, p, p, p, i, i, i]
     lib.oa_head_argmax.restype = i
     # probe/test entry: explicit K depth

@@ -303,3 +303,122 @@ def head_argmax(
     if mask is not None:
         tok = torch.where(mask.any(dim=-1), tok, torch.full_like(tok, -1))
     return tok
+
+
+def philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 on numpy uint32 counter arrays; returns four uint32
+    arrays. Integer arithmetic only (64-bit products, masked)."""
+    import numpy as np
+
+    M = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & M for c in (c0, c1, c2, c3))
+    k0 = np.uint64(k0 & 0xFFFFFFFF)
+    k1 = np.uint64(k1 & 0xFFFFFFFF)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c0
+        p1 = np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (
+            (p1 >> np.uint64(32)) ^ c1 ^ k0,
+            p1 & M,
+            (p0 >> np.uint64(32)) ^ c3 ^ k1,
+            p0 & M,
+        )
+        k0 = (k0 + np.uint64(0x9E3779B9)) & M
+        k1 = (k1 + np.uint64(0xBB67AE85)) & M
+    return tuple(c.astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
+def sample_masked(
+    logits: torch.Tensor,
+    mask: Optional[torch.Tensor],
+    inv_temp: torch.Tensor,
+    top_k: torch.Tensor,
+    top_p: torch.Tensor,
+    seed: torch.Tensor,
+    step: torch.Tensor,
+    adj: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+    info: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Seeded sampler, the twin of sample.hip: mask first, then sparse
+    adjustments, top-k by value, top-p by value level, Gumbel-max draw with
+    Philox noise keyed by (seed, step, token). fp32 where the kernel is fp32,
+    top-p masses as w * 2^40 integers. logits [B, V]; mask [B, V] bool or
+    None; inv_temp f32, top_k i32, top_p f32, seed/step int64 (the u64 bits)
+    [B]; adj = (adj_ptr i32 [B+1], adj_tok i32 [nnz], adj_val f32 [nnz]),
+    tokens sorted and unique per row. Returns int64 [B], -1 where no
+    candidate exists; fills info int32 [B, 2] (kept count, bits of the
+    smallest kept z) when given."""
+    import numpy as np
+
+    B, V = logits.shape
+    x = logits.detach().float().cpu().numpy()
+    m = None if mask is None else mask.detach().cpu().numpy().astype(bool)
+    it_a = inv_temp.detach().cpu().numpy().astype(np.float32)
+    k_a = top_k.detach().cpu().numpy().astype(np.int64)
+    p_a = top_p.detach().cpu().numpy().astype(np.float32)
+    seed_a = seed.detach().cpu().numpy().astype(np.int64).view(np.uint64)
+    step_a = step.detach().cpu().numpy().astype(np.int64).view(np.uint64)
+    if adj is not None:
+        aptr = adj[0].detach().cpu().numpy()
+        atok = adj[1].detach().cpu().numpy()
+        aval = adj[2].detach().cpu().numpy().astype(np.float32)
+    out = np.full(B, -1, dtype=np.int64)
+    inf_bits = 0x7F800000
+    info_np = np.zeros((B, 2), dtype=np.int32)
+    info_np[:, 1] = inf_bits
+    for b in range(B):
+        z = x[b].copy()
+        if adj is not None:
+            a0, a1 = int(aptr[b]), int(aptr[b + 1])
+            ok = (atok[a0:a1] >= 0) & (atok[a0:a1] < V)
+            t = atok[a0:a1][ok]
+            z[t] = z[t] + aval[a0:a1][ok]  # one fp32 add
+        with np.errstate(invalid="ignore"):
+            cand = z > -np.inf  # false for NaN
+        if m is not None:
+            cand &= m[b]
+        ncand = int(cand.sum())
+        if ncand == 0:
+            continue
+        it, k, p = it_a[b], int(k_a[b]), p_a[b]
+        zc = np.where(cand, z, -np.inf).astype(np.float32)
+        if not it > 0:
+            win = int(np.argmax(zc))
+            out[b] = win
+            info_np[b] = (ncand, int(z[win : win + 1].view(np.int32)[0]))
+            continue
+        keep = cand.copy()
+        zmax = zc.max()
+        if 0 < k < ncand:
+            tau = np.partition(zc, V - k)[V - k]
+            keep &= zc >= tau
+        if p < 1.0:
+            idx = np.nonzero(keep)[0]
+            zk = zc[idx]
+            s = (zk * it).astype(np.float32)
+            smax = np.float32(zmax * it)
+            w = np.exp((s - smax).astype(np.float32)).astype(np.float32)
+            wfix = np.rint(w.astype(np.float64) * 2.0**40).astype(np.int64)
+            lev, inv = np.unique(zk, return_inverse=True)  # ascending
+            mass = np.zeros(lev.shape[0], dtype=np.int64)
+            np.add.at(mass, inv, wfix)
+            Z = int(mass.sum())
+            limit = int(float(p) * float(Z)) if p > 0 else 0
+            above = Z - np.cumsum(mass)  # mass strictly above each level
+            ok = (above <= limit) & (mass > 0)
+            tau = lev[np.nonzero(ok)[0][0]]
+            keep &= zc >= tau
+        idx = np.nonzero(keep)[0]
+        sd, st = int(seed_a[b]), int(step_a[b])
+        words = philox4x32_10(
+            idx >> 2, st & 0xFFFFFFFF, st >> 32, 0, sd & 0xFFFFFFFF, sd >> 32
+        )
+        r = np.choose(idx & 3, words)
+        u = ((2 * (r >> 9) + 1).astype(np.float32) * np.float32(2.0**-24)).astype(np.float32)
+        g = (-np.log(-np.log(u))).astype(np.float32)
+        key = ((zc[idx] * it).astype(np.float32) + g).astype(np.float32)
+        out[b] = int(idx[int(np.argmax(key))])
+        info_np[b] = (idx.shape[0], int(zc[idx].min(keepdims=True).view(np.int32)[0]))
+    if info is not None:
+        info.copy_(torch.from_numpy(info_np).to(info.device))
+    return torch.from_numpy(out)

@@ -436,6 +436,7 @@ def create_app(cfg: Optional[Config] = None) -> FastAPI:
                         presence_penalty=float(body.get("presence_penalty", 0.0)),
                         frequency_penalty=float(body.get("frequency_penalty", 0.0)),
                         logit_bias=body.get("logit_bias"),
+                        seed=body.get("seed"),
                     ):
                         yield f"data: {json.dumps(chunk)}\n\n"
                     yield "data: [DONE]\n\n"
@@ -454,6 +455,7 @@ def create_app(cfg: Optional[Config] = None) -> FastAPI:
                     tools=body.get("tools"),
                     tool_choice=body.get("tool_choice"),
                     temperature=float(body.get("temperature", 0.0)),
+                    seed=body.get("seed"),
                 )
                 ch = resp["choices"][0]
 
@@ -490,6 +492,7 @@ def create_app(cfg: Optional[Config] = None) -> FastAPI:
                 logprobs=bool(body.get("logprobs", False)),
                 top_logprobs=int(body.get("top_logprobs", 0)),
                 tool_choice=body.get("tool_choice"),
+                seed=body.get("seed"),
             )
             return resp
         except Exception as e:  # noqa: BLE001
