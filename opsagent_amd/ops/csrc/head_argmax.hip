@@ -54,9 +54,11 @@ __device__ __forceinline__ uint32_t head_ordered_f32(float f) {
     return (v.u & 0x80000000u) ? ~v.u : (v.u | 0x80000000u);
 }
 
+// best + 0.0f turns -0 into +0: the wave compared floats, where -0 == +0 and
+// the lowest index wins; the packed key alone would order -0 below +0
 __device__ __forceinline__ u64 head_key(float best, int besti) {
     return besti < 0 ? 0ull
-                     : ((u64)head_ordered_f32(best) << 32) |
+                     : ((u64)head_ordered_f32(best + 0.0f) << 32) |
                            (unsigned)(0x7fffffff - besti);
 }
 

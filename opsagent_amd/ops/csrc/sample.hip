@@ -52,8 +52,8 @@ namespace {
 
 typedef unsigned long long u64;
 
-// the same map as ordered_f32 in sampling.hip (left untouched): greedy rows must
-// agree with masked_argmax bit for bit, tests/test_sampling_gpu.py holds them to it
+// the same map as ordered_f32 in sampling.hip: greedy rows must agree with
+// masked_argmax bit for bit, tests/test_sampling_gpu.py holds them to it
 __device__ __forceinline__ uint32_t sample_ord(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -276,7 +276,9 @@ __device__ __forceinline__ Red pass0_scan(const Row& r) {
         for (int j = 0; j < 4; ++j) {
             if ((live >> j) & 1u) {
                 v.cnt++;
-                const u64 key = ((u64)sample_ord(z[j]) << 32) | (uint32_t)(0x7fffffff - (t0 + j));
+                // z + 0.0f: -0 ties with +0 and the lowest index wins, as in masked_argmax
+                const u64 key =
+                    ((u64)sample_ord(z[j] + 0.0f) << 32) | (uint32_t)(0x7fffffff - (t0 + j));
                 v.best = key > v.best ? key : v.best;
             }
         }

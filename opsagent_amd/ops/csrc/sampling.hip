@@ -79,10 +79,12 @@ __global__ __launch_bounds__(256) void masked_argmax_scan(
     }
     __shared__ unsigned long long sbest[4];
     const int wid = threadIdx.x / WAVE;
+    // best + 0.0f turns -0 into +0: up to here floats were compared, where
+    // -0 == +0 and the lowest index wins; the packed key orders -0 below +0
     if ((threadIdx.x & (WAVE - 1)) == 0)
         sbest[wid] = besti < 0
                          ? 0ull
-                         : ((unsigned long long)ordered_f32(best) << 32) |
+                         : ((unsigned long long)ordered_f32(best + 0.0f) << 32) |
                                (unsigned)(0x7fffffff - besti);
     __syncthreads();
     if (threadIdx.x == 0) {

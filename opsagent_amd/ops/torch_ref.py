@@ -285,11 +285,14 @@ def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor) -> torc
 
 
 def greedy_sample_masked(logits: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
-    """argmax over allowed tokens. logits [B, V]; mask [B, V] bool (True = allowed)."""
+    """argmax over allowed tokens. logits [B, V]; mask [B, V] bool (True = allowed).
+    The largest by IEEE comparison (-0 equals +0), the lowest index among
+    equals, -1 where no allowed logit is > -inf, as the kernel gives."""
     lf = logits.float()
     if mask is not None:
         lf = lf.masked_fill(~mask, float("-inf"))
-    return lf.argmax(dim=-1)
+    tok = lf.argmax(dim=-1)
+    return torch.where((lf > float("-inf")).any(dim=-1), tok, torch.full_like(tok, -1))
 
 
 def head_argmax(
@@ -297,12 +300,9 @@ def head_argmax(
 ) -> torch.Tensor:
     """Greedy decode head: linear, rounded to bf16 as the logits row is, then
     the masked greedy pick. x [M, K]; w [V, K]; mask [M, V] bool or None.
-    Returns int64 [M], -1 where no token is allowed."""
+    Returns int64 [M], -1 where no allowed logit is > -inf."""
     logits = torch.nn.functional.linear(x, w).to(torch.bfloat16)
-    tok = greedy_sample_masked(logits, mask)
-    if mask is not None:
-        tok = torch.where(mask.any(dim=-1), tok, torch.full_like(tok, -1))
-    return tok
+    return greedy_sample_masked(logits, mask)
 
 
 def philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
@@ -385,7 +385,8 @@ def sample_masked(
         if not it > 0:
             win = int(np.argmax(zc))
             out[b] = win
-            info_np[b] = (ncand, int(z[win : win + 1].view(np.int32)[0]))
+            # the kernel's key holds z + 0: a winning -0 is reported as +0
+            info_np[b] = (ncand, int((z[win : win + 1] + np.float32(0)).view(np.int32)[0]))
             continue
         keep = cand.copy()
         zmax = zc.max()

@@ -9,6 +9,10 @@ Every case asserts two things:
       largest allowed fp64 logit — this catches both paths being wrong
       together.
 
+test_signed_zero_and_neg_inf_rows builds logits that are exactly -0, +0 and
+-inf and holds both paths to the rule of tests/argmax_cases.py: -0 ties with
++0, the lowest index wins, -inf is never chosen.
+
 Bound of (b): the kernel compares logits rounded to bf16 (8 significand bits),
 so the chosen and the best row may differ by one bf16 step at the larger of
 their magnitudes, 2^(floor(log2 |v|) - 7). The fp32 value that is rounded
@@ -190,6 +194,83 @@ def test_ties_lowest_index_wins(V, K, M):
     a[:, rows[2:]] = True
     out = _check("tie2", c, w2, lg2, ad2, a, _pack(a))
     assert out.tolist() == [rows[2]] * M
+
+
+@pytest.mark.parametrize("M", [1, 2])
+@pytest.mark.parametrize("V,K", SHAPES)
+def test_signed_zero_and_neg_inf_rows(V, K, M):
+    """The rule of masked_argmax holds in the head too: -0 ties with +0 and the
+    lowest index wins, wherever the two rows fall in the grid, and a row whose
+    logit is -inf is never chosen (-1 if nothing else is allowed).
+
+    The logits are exact by construction. Column k0 of x is 2^-70, column k1
+    is 2^64 and column k1 of W is zero. A W row that is zero but for -2^-70 at
+    k0 gives -2^-140, which rounds to bf16 -0; a zero row gives +0; a zero row
+    with -2^100 at k1 overflows fp32 to -inf. Every other allowed logit is
+    negative. Fused and unfused must both give the oracle's token."""
+    from opsagent_amd import ops
+
+    c = _case(V, K, M)
+    nwaves = 4 * ops.head_argmax_grid(V, M)
+    later = 2 * nwaves + 4 if 2 * nwaves + 4 < V else V // 2 + 1
+    rows = sorted({2, 3, 25, later, V - 3})
+    assert len(rows) == 5
+    k0, k1 = 5, K - 3
+    x = c["x"].clone()
+    x[:, k0], x[:, k1] = 2.0 ** -70, 2.0 ** 64
+    base = c["w"].clone()
+    base[:, k1] = 0
+    negz = torch.zeros(K, dtype=torch.bfloat16)
+    negz[k0] = -(2.0 ** -70)
+    posz = torch.zeros(K, dtype=torch.bfloat16)
+    ninf = torch.zeros(K, dtype=torch.bfloat16)
+    ninf[k1] = -(2.0 ** 100)
+    bits = {"negz": -0x8000, "posz": 0, "ninf": -0x80}            # bf16 bits as int16
+    background = x.cpu().double() @ base.cpu().double().t()       # [M, V]
+    negative = background < -1e-3
+
+    def run(plant, allowed_rows, want):
+        w = base.clone()
+        for r, kind in plant.items():
+            w[r] = {"negz": negz, "posz": posz, "ninf": ninf}[kind].cuda()
+        lg = ops.linear(x, w)
+        for r, kind in plant.items():
+            assert (lg[:, r].view(torch.int16).cpu() == bits[kind]).all(), (kind, lg[:, r])
+        a = negative.clone()
+        a[:, rows] = False
+        a[:, allowed_rows] = True
+        mask = _pack(a)
+        fused = ops.head_argmax(x, w, mask).cpu().tolist()
+        unfused = ops.greedy_sample_masked(lg, mask).cpu().tolist()
+        print(f"{plant} allowed {allowed_rows}: fused {fused} unfused {unfused} want {want}")
+        assert fused == [want] * M and unfused == [want] * M
+
+    for low, rest in (("negz", "posz"), ("posz", "negz")):
+        plant = {r: (low if r == rows[0] else rest) for r in rows}
+        run(plant, rows, rows[0])
+        run(plant, rows[1:], rows[1])
+        run(plant, rows[2:], rows[2])
+        run(plant, rows[3:], rows[3])
+    # pairs of one +0 and one -0 only: the same wave, two waves, two trips
+    for lo, hi in ((rows[0], rows[1]), (rows[0], rows[2]), (rows[2], rows[3]), (rows[3], rows[4])):
+        for a_kind, b_kind in (("negz", "posz"), ("posz", "negz")):
+            plant = {r: "ninf" for r in rows}
+            plant[lo], plant[hi] = a_kind, b_kind
+            run(plant, rows, lo)
+    ones = torch.zeros(M, V, dtype=torch.bool)
+    ones[:, rows] = True
+    w = base.clone()
+    for r in rows:
+        w[r] = ninf.cuda()
+    mask = _pack(ones)                                            # every allowed logit is -inf
+    assert ops.head_argmax(x, w, mask).cpu().tolist() == [-1] * M
+    assert ops.greedy_sample_masked(ops.linear(x, w), mask).cpu().tolist() == [-1] * M
+    lone = 9                                                      # -inf beside one finite logit
+    assert lone not in rows
+    ones[:, lone] = True
+    mask = _pack(ones)
+    assert ops.head_argmax(x, w, mask).cpu().tolist() == [lone] * M
+    assert ops.greedy_sample_masked(ops.linear(x, w), mask).cpu().tolist() == [lone] * M
 
 
 @pytest.mark.parametrize("V,K", SHAPES)

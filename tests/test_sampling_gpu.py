@@ -159,6 +159,27 @@ def test_greedy_rows_equal_masked_argmax(V):
         got = ops.sample_masked(logits, mk, zeros_f, zeros_i, ones_f, z64, z64)
         want = ops.greedy_sample_masked(logits, mk)
         assert torch.equal(got.cpu(), want.cpu())
+    # the rule itself, on rows of tests/argmax_cases.py: -0 ties with +0 and the
+    # lowest index wins wherever the pair falls, all -inf and nothing allowed give -1
+    import argmax_cases as ac
+
+    for masked in (False, True):
+        rs = [r for r in ac.rows(V, masked)
+              if r.name.startswith("zero_") or r.name in ("allowed_all_neg_inf", "nothing_allowed",
+                                                          "neg_inf_beside_finite")]
+        B = len(rs)
+        logits = torch.from_numpy(np.stack([r.logits for r in rs])).to(torch.bfloat16).cuda()
+        mk = None
+        if masked:
+            words = np.stack([ac.pack_mask(r.mask, r.high_bits) for r in rs]).view(np.int32)
+            mk = torch.from_numpy(words.copy()).cuda()
+        zf = torch.zeros(B, dtype=torch.float32, device="cuda")
+        z64 = torch.zeros(B, dtype=torch.int64, device="cuda")
+        got = ops.sample_masked(logits, mk, zf, torch.zeros(B, dtype=torch.int32, device="cuda"),
+                                zf + 1, z64, z64)
+        want = ops.greedy_sample_masked(logits, mk)
+        assert got.cpu().tolist() == [r.expect for r in rs]
+        assert want.cpu().tolist() == [r.expect for r in rs]
 
 
 def test_launcher_rejects_v_not_multiple_of_8():
