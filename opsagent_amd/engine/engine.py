@@ -857,7 +857,9 @@ class LLMEngine:
             self.spec_decode
             and (req.grammar_state is None or self.spec_grammar)
             and not req.params.logprobs
-            and req.params.temperature == 0.0
+            # the verify pass takes the argmax of the RAW logits: a row with
+            # a bias, a penalty or a temperature is sampled step by step
+            and not req.params.needs_logit_transform()
             and (
                 self.spec_ema >= self.spec_min_ema
                 # workloads change: re-probe periodically after the EMA

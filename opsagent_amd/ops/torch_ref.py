@@ -14,11 +14,17 @@ from typing import Optional, Tuple
 import torch
 
 
+def _acc(x: torch.Tensor) -> torch.Tensor:
+    """Working precision: fp32, or fp64 for an fp64 input (a model built in
+    fp64 is then fp64 throughout, which the whole-model oracle test uses)."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     dtype = x.dtype
-    xf = x.float()
+    xf = _acc(x)
     var = xf.pow(2).mean(dim=-1, keepdim=True)
-    out = xf * torch.rsqrt(var + eps) * weight.float()
+    out = xf * torch.rsqrt(var + eps) * weight.to(xf.dtype)
     return out.to(dtype)
 
 
@@ -26,7 +32,7 @@ def fused_add_rms_norm(
     x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Returns (rmsnorm(x + residual), x + residual)."""
-    s = (x.float() + residual.float())
+    s = (_acc(x) + _acc(residual))
     out = rms_norm(s, weight, eps)
     return out.to(x.dtype), s.to(x.dtype)
 
@@ -56,17 +62,17 @@ def rope_apply(
     """
     def _rot(x: torch.Tensor) -> torch.Tensor:
         d = x.shape[-1]
-        c = cos[positions].to(torch.float32).unsqueeze(1)  # [T,1,D/2]
-        s = sin[positions].to(torch.float32).unsqueeze(1)
-        x1 = x[..., : d // 2].float()
-        x2 = x[..., d // 2 :].float()
+        x1 = _acc(x[..., : d // 2])
+        x2 = _acc(x[..., d // 2 :])
+        c = cos[positions].to(x1.dtype).unsqueeze(1)  # [T,1,D/2]
+        s = sin[positions].to(x1.dtype).unsqueeze(1)
         return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).to(x.dtype)
 
     return _rot(q), _rot(k)
 
 
 def silu_mul(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
-    return (torch.nn.functional.silu(gate.float()) * up.float()).to(gate.dtype)
+    return (torch.nn.functional.silu(_acc(gate)) * _acc(up)).to(gate.dtype)
 
 
 def attention_prefill(
@@ -86,9 +92,9 @@ def attention_prefill(
     Hk, Skv = k.shape[1], k.shape[2]
     scale = scale if scale is not None else D ** -0.5
     group = Hq // Hk
-    kf = k.float().repeat_interleave(group, dim=1)
-    vf = v.float().repeat_interleave(group, dim=1)
-    s = torch.einsum("bhqd,bhkd->bhqk", q.float(), kf) * scale
+    kf = _acc(k).repeat_interleave(group, dim=1)
+    vf = _acc(v).repeat_interleave(group, dim=1)
+    s = torch.einsum("bhqd,bhkd->bhqk", _acc(q), kf) * scale
     if causal:
         offset = Skv - Sq
         qi = torch.arange(Sq, device=q.device).unsqueeze(1)
@@ -125,11 +131,11 @@ def attention_decode_paged(
         n = int(seq_lens[b].item())
         nblocks = (n + block_size - 1) // block_size
         blocks = block_table[b, :nblocks].long()
-        k = k_cache[blocks].reshape(-1, Hk, D)[:n].float()  # [n, Hk, D]
-        v = v_cache[blocks].reshape(-1, Hk, D)[:n].float()
+        k = _acc(k_cache[blocks].reshape(-1, Hk, D)[:n])  # [n, Hk, D]
+        v = _acc(v_cache[blocks].reshape(-1, Hk, D)[:n])
         kf = k.repeat_interleave(group, dim=1)  # [n, Hq, D]
         vf = v.repeat_interleave(group, dim=1)
-        s = torch.einsum("hd,nhd->hn", q[b].float(), kf) * scale
+        s = torch.einsum("hd,nhd->hn", _acc(q[b]), kf) * scale
         p = torch.softmax(s, dim=-1)
         outs.append(torch.einsum("hn,nhd->hd", p, vf))
     return torch.stack(outs).to(q.dtype)
