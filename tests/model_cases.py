@@ -126,7 +126,8 @@ def _bf16(x):
 def forward(W: dict, tokens, pos=None, count=None, zeros=None, *, dtype=torch.float64,
             rnd: bool = False, rows=None, no_resid_attn=False, resid_twice=False,
             head_shift=False, k_unroped=False, kv_prev_layer=False,
-            want_logits=True):
+            want_logits=True, forced=None, gathered=None, alt=None, device=None,
+            want_kv=False):
     """fp64 forward of the entries (dtype/rnd give the emulations: fp32, and
     fp32 with a bf16 rounding wherever a correct GPU path stores bf16).
     Returns (final-norm hidden [T, H], logits [T, V]).
@@ -134,7 +135,16 @@ def forward(W: dict, tokens, pos=None, count=None, zeros=None, *, dtype=torch.fl
     Mutant knobs act on the entries `rows` (default all): residual not
     updated after attention, residual added twice behind the o projection,
     q-head h on kv-head (h+1)//G, cached K read un-roped, cached K/V of the
-    layer below. "Cached" is every key but the entry's own."""
+    layer below. "Cached" is every key but the entry's own.
+
+    The fp8 cache (tests/model_fp8_cases.py): `forced` is a per-layer list of
+    (K, V) [T, Hk, D] that every entry attends in place of the computed k and
+    v, its own key included; `gathered` marks the rows that read those values
+    rounded to bf16 (the prefill gather; emulation only); `alt` = (mask
+    [T, T], kv) reads the pairs (row, key) of the mask from kv[layer], or from
+    the entries' own unquantised k and v where kv is None; `device(layer, k,
+    v, k_raw)` returns the (K, V) a simulated cache gives back. With want_kv
+    the entries' own roped k and v per layer are returned as a third value."""
     r = _bf16 if rnd else (lambda x: x)
     tok = torch.as_tensor(list(tokens), dtype=torch.long)
     T = tok.numel()
@@ -165,6 +175,7 @@ def forward(W: dict, tokens, pos=None, count=None, zeros=None, *, dtype=torch.fl
     resid = W["embed"][tok].to(dtype)
     pend = torch.zeros_like(resid)       # MLP output awaiting the fused add
     prev_kv = None
+    own = []                             # per layer: the entries' own roped k and v
     for L in W["layers"]:
         s0 = resid + pend                # the norm reads the unrounded sum
         h = r(norm(s0, L["in_w"]))
@@ -174,6 +185,12 @@ def forward(W: dict, tokens, pos=None, count=None, zeros=None, *, dtype=torch.fl
         k_raw = qkv[:, hq * hd: (hq + hk) * hd].reshape(T, hk, hd)
         v = qkv[:, (hq + hk) * hd:].reshape(T, hk, hd)
         q, k = r(rope(q)), r(rope(k_raw))
+        k_own, v_own = k, v
+        own.append((k_own, v_own))
+        if device is not None:
+            k, v = device(len(own) - 1, k, v, k_raw)
+        if forced is not None:
+            k, v = (t.to(dtype) for t in forced[len(own) - 1])
         qh = q.permute(1, 0, 2)                                   # [hq, T, D]
 
         def scores(K, hmap):
@@ -188,8 +205,15 @@ def forward(W: dict, tokens, pos=None, count=None, zeros=None, *, dtype=torch.fl
         if kv_prev_layer and prev_kv is not None:
             Kc, Vc = prev_kv
         cached = (rows[:, None] & ~eye)[None]                     # [1, T, T]
+        if alt is not None:
+            cached = alt[0][None]
+            Kc, Vc = (k_own, v_own) if alt[1] is None else (
+                t.to(dtype) for t in alt[1][len(own) - 1])
         if Kc is not None:
             s = torch.where(cached, scores(Kc, kvh_true), s)
+        if gathered is not None and rnd:
+            assert Kc is None and not head_shift
+            s = torch.where(gathered[None, :, None], scores(_bf16(k), kvh_true), s)
         live = (count > 0)[None]
         s = torch.where(live, s, torch.full_like(s, float("-inf")))
         m = s.amax(dim=-1, keepdim=True)
@@ -207,6 +231,9 @@ def forward(W: dict, tokens, pos=None, count=None, zeros=None, *, dtype=torch.fl
             o = pv(p - pc, v, kvh_true) + pv(pc, Vc, kvh_true)
         elif head_shift:
             o = torch.where(rows[None, :, None], pv(p, v, kvh), pv(p, v, kvh_true))
+        elif gathered is not None and rnd:
+            o = torch.where(gathered[None, :, None], pv(p, _bf16(v), kvh_true),
+                            pv(p, v, kvh_true))
         else:
             o = pv(p, v, kvh_true)
         o = torch.where(l > 0, o / l.clamp_min(1e-300), torch.zeros_like(o))
@@ -225,6 +252,8 @@ def forward(W: dict, tokens, pos=None, count=None, zeros=None, *, dtype=torch.fl
         pend = r(act @ L["down"].to(dtype).T)
     hidden = r(norm(resid + pend, W["final_w"]))
     logits = r(hidden @ W["lm_head"].to(dtype).T) if want_logits else None
+    if want_kv:
+        return hidden, logits, own
     return hidden, logits
 
 
@@ -292,6 +321,7 @@ class Record:
     call: int                   # index of the forward it came from
     idx: int                    # row index inside that forward's head input
     sampled: Optional[int] = None   # token sampled from this row, if any
+    slot: int = -1                  # flat cache slot the row's K/V went to
 
 
 class Recorder:
@@ -384,7 +414,7 @@ class Recorder:
             mine.append(tok)
             prefix = tuple(toks[: first[req.req_id]]) + tuple(mine)
             self.records.append(Record(prefix, label, len(run), len(ids), False,
-                                       rows[t], req.req_id, p, call, t))
+                                       rows[t], req.req_id, p, call, t, slot=s))
         B = len(run)
         for r in self.records[-len(ids):]:
             r.B = B
@@ -396,6 +426,10 @@ class Recorder:
         else:
             head_rows = [len(ids) - 1]
         self.calls.append(dict(kind=kind, hidden=rows, head_rows=head_rows))
+        self._after_rows(self.records[-len(ids):])
+
+    def _after_rows(self, recs):
+        """Called with the new records once their forward has returned."""
 
     def _wrap_decode(self, name, graphed):
         orig = getattr(self.e, name)
@@ -420,8 +454,9 @@ class Recorder:
                 toks = req.seq.token_ids
                 assert p + 1 == len(toks) and toks[p] == tok
                 self.records.append(Record(tuple(toks), "decode", B, bucket, was_graphed,
-                                           rows[i], req.req_id, p, call, i))
+                                           rows[i], req.req_id, p, call, i, slot=s))
             self.calls.append(dict(kind="decode", hidden=rows, head_rows=list(range(B))))
+            self._after_rows(self.records[-B:])
             return hidden
 
         setattr(self.e, name, w)
@@ -726,9 +761,9 @@ SCENARIOS = {
 }
 
 
-def run_scenario(name: str, engine, exact: bool = False):
+def run_scenario(name: str, engine, exact: bool = False, recorder=Recorder):
     """Runs one scenario on a fresh Recorder. Returns (recorder, params)."""
-    rec = Recorder(engine)
+    rec = recorder(engine)
     try:
         V = engine.spec.vocab_size
         ps = sc_verify(rec, V, exact) if name == "verify" else SCENARIOS[name](rec, V)
